@@ -34,6 +34,17 @@ payloads over the ranks (RCCL; a no-op on one GPU) and take the cross-frame vote
                                     stays what this one GPU really processed.
 `collective.ranks` / `rccl_ranks` = what an all-reduce of ones returned: the ranks the collective library really joined.
 
+A plain run does what the headline figure needs and nothing more: set-up (placement probe, pre-heat), W warm-up steps, K timed steps
+(no event pairs on their launches), the payload / vote check of the timed steps, one JSON line (`value`, `ms_per_step`, `config`,
+`payload_bit_exact`, `path` without its measured-copy fraction; `roofline`, `cpu_baseline` and the HBM rates null).  `--full` adds
+the figures described below beside `value`: `value_no_preheat`, the second pass, the side measurements, per-kernel durations and
+`roofline` (event pairs on the timed launches), the HBM probes, the CPU baseline and `oracle_check`.
+  --dump-outputs DIR    after the timed steps, what the LAST timed step computed, as DIR/<name>.npy: `payloads` (this rank's
+                        per-frame payload bits [n, L], float32), `vote_payloads` / `vote_frequencies` (every segment's vote,
+                        [segments, L] float32 / [segments] float64), and the marked output: `marked` (the whole output, float32)
+                        or, above 2^23 elements, `marked_sample` (the elements at np.unique(np.random.default_rng(0).integers(0,
+                        numel, 2^23)) of the flattened output, float32).  Same arguments, same inputs: two builds compare file by file.
+
 Small shards (a 48-frame segment is 0.2 ms of GPU work, less than the host needs to issue a step): `--group G` (default: auto)
 issues G steps per host iteration -- the G steps' kernels are replayed as ONE captured hipGraph, their payloads are gathered
 and downloaded once, and the host votes on all G steps' payloads in one vectorised call; every step still embeds, detects,
@@ -88,6 +99,7 @@ import numpy as np  # noqa: E402
 HBM_PEAK_GBPS = 8000.0        # MI355X HBM3E spec (MI355X_MICROARCH.md); ~6300 GB/s is achievable
 PAYLOAD = np.array([0, 1, 1, 0, 0, 1, 0, 1])
 GRAPH_BELOW_BYTES = 100 * 1080 * 1920 * 3      # shards under 100 frames of 1080p: capture the step(s) as a hipGraph
+DUMP_SAMPLE_ELEMS = 1 << 23                     # --dump-outputs: a larger marked output is written as this many seeded elements (32 MiB)
 
 
 def parse():
@@ -140,7 +152,16 @@ def parse():
                     help="do not attach HIP events to the kernel launches (roofline becomes null)")
     ap.add_argument("--no-extras", action="store_true", help="skip the side measurements")
     ap.add_argument("--cpu-seconds", type=float, default=8.0, help="budget of the CPU baseline's main (C, all cores) sample")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline figure: the no-preheat pass, second pass, side measurements, per-kernel "
+                         "event timings and roofline, HBM probes, CPU baseline and oracle check (a plain run times the K steps only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32 / float64, at most "
+                         "64 MB in all; a larger output is written as a fixed, seeded sample of its elements)")
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    return a
 
 
 def source_sha16():
@@ -437,6 +458,17 @@ def plugin_yuv32f_rates(H, W, alpha, frame_u8):
     return out
 
 
+def write_outputs(out_dir, arrays):
+    """--dump-outputs: every array as out_dir/<name>.npy, device tensors downloaded; u8 frames and payload bits as float32."""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, arr in arrays.items():
+        if not isinstance(arr, np.ndarray):
+            arr = arr.cpu().numpy()
+        if arr.dtype not in (np.float32, np.float64):
+            arr = arr.astype(np.float32)
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
+
+
 class stdout_to_stderr:
     """File-descriptor-level redirection of stdout into stderr for the duration of a block: native libraries print there
     (RCCL writes a five-line version banner to STDOUT when its first communicator comes up), and this program's stdout
@@ -582,6 +614,11 @@ def launch_ranks(a):
 
 def main():
     a = parse()
+    if not a.full:
+        # a plain run does what `value` / `ms_per_step` need and nothing else: set-up (placement probe, pre-heat), W warm-up steps,
+        # K timed steps, the payload / vote check of the timed steps.  No event pairs on the timed launches, no side measurements,
+        # no HBM probes, no CPU baseline (--full restores every one of them)
+        a.no_extras = a.no_cpu_baseline = a.no_kernel_events = True
     if a.emulate_world and a.gpus != 1:
         raise SystemExit("--emulate-world needs --gpus 1 (it rehearses rank 0 of an M-rank job on ONE GPU)")
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -868,6 +905,14 @@ def main():
                 el = float(t.item())
             return el, votes, size
 
+        def last_step_buffers(self, size):
+            """(marked frames or None, payloads [n, L]) the LAST step of the group issued last wrote: slot size - 1, and in a graphed
+            group with two branches an even slot count puts that step on the second branch (StepPipeline.capture)."""
+            lane, par = self.last
+            graphed = self.use_graph and size == self.G and self.n and self.graph_allowed(lane)
+            second = graphed and lane.eng2 is not None and (size - 1) % 2 == 1
+            return (lane.out2 if second else lane.out), lane.pay[par, size - 1]
+
         def votes_ok(self, votes, size):
             """every step of the (last) group: every segment's vote equals its payload (config 5: and the leak's copy sequence)."""
             j = self.j
@@ -925,6 +970,13 @@ def main():
             p1 = lanes[0].pay[0, :1].reshape(-1, L)
             gather_payloads(p1.cpu() if a.backend == "gloo" else p1, equal_shards=job.equal, force=grouped)
         torch.cuda.synchronize()
+    # --dump-outputs: which elements of the marked output are written, fixed in set-up (host work here, never between the warm-up and
+    # the timed steps); the whole output when it fits
+    dump_idx = None
+    if a.dump_outputs and lanes[0].out is not None and n:
+        numel = lanes[0].out.numel()
+        if numel > DUMP_SAMPLE_ELEMS:
+            dump_idx = torch.from_numpy(np.unique(np.random.default_rng(0).integers(0, numel, DUMP_SAMPLE_ELEMS))).to(dev)
     # the contract read literally -- W warm-up steps from idle, then K timed steps -- before the pre-heat, so that figure stays
     # available next to `value`: `value_no_preheat`.  Same fences, same collectives, every rank.
     cold = None
@@ -940,6 +992,17 @@ def main():
     inject_failure("timed", rank)
     elapsed, votes, last_size = runner.timed(a.steps)
     own_elapsed = runner.own_elapsed
+    dump = None
+    if a.dump_outputs:          # device-side copies of what the last timed step returned (the side measurements reuse its buffers)
+        out_last, pay_last = runner.last_step_buffers(last_size)
+        dump = dict(payloads=pay_last.clone())
+        if out_last is not None and n:
+            dump["marked_sample" if dump_idx is not None else "marked"] = out_last.reshape(-1)[dump_idx] if dump_idx is not None else out_last.clone()
+        segs = sorted(job.expected)
+        last_votes = [votes.get((last_size - 1) * runner.S_ids + s if last_size > 1 else s) for s in segs]
+        dump["vote_payloads"] = np.stack([np.asarray(v[0], np.float32) if v is not None and v[0] is not None else np.full(L, np.nan, np.float32)
+                                          for v in last_votes])
+        dump["vote_frequencies"] = np.array([v[1] if v is not None and v[0] is not None else np.nan for v in last_votes], np.float64)
     shipped_order = lanes[0].eng.tile_order                  # what the timed region ran with
     shipped_info = lanes[0].eng.tile_order_info
     host_ms = {k: round(1e3 * v / a.steps, 4) for k, v in runner.host_s.items()}
@@ -1296,34 +1359,36 @@ def main():
         except Exception as exc:
             extra["plugin_yuv32f"] = dict(error=repr(exc))
 
-    # achievable HBM bandwidth of this device, same run: 16-byte streaming copy (read + write) and read-only stream
-    out0 = lanes[0].out
-    if job.frames.numel() >= (1 << 28) and out0 is not None and out0.numel() == job.frames.numel():
-        probe_src, probe_dst = job.frames, out0
-    else:
-        probe_src = torch.empty(1 << 30, dtype=torch.uint8, device=dev).random_(0, 256)
-        probe_dst = torch.empty_like(probe_src)
-    nbytes = probe_src.numel() // 16 * 16
-    sink = torch.zeros(4, dtype=torch.int32, device=dev)
-    s = _hip.current_stream()
+    # achievable HBM bandwidth of this device, same run: 16-byte streaming copy (read + write) and read-only stream (--full)
+    copy_gbps = read_gbps = None
+    if a.full:
+        out0 = lanes[0].out
+        if job.frames.numel() >= (1 << 28) and out0 is not None and out0.numel() == job.frames.numel():
+            probe_src, probe_dst = job.frames, out0
+        else:
+            probe_src = torch.empty(1 << 30, dtype=torch.uint8, device=dev).random_(0, 256)
+            probe_dst = torch.empty_like(probe_src)
+        nbytes = probe_src.numel() // 16 * 16
+        sink = torch.zeros(4, dtype=torch.int32, device=dev)
+        s = _hip.current_stream()
 
-    def probe(fn, moved):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        for _ in range(2):
-            fn()
-        e0.record()
-        for _ in range(5):
-            fn()
-        e1.record()
-        torch.cuda.synchronize()
-        return 5 * moved / (e0.elapsed_time(e1) * 1e-3) / 1e9
+        def probe(fn, moved):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            for _ in range(2):
+                fn()
+            e0.record()
+            for _ in range(5):
+                fn()
+            e1.record()
+            torch.cuda.synchronize()
+            return 5 * moved / (e0.elapsed_time(e1) * 1e-3) / 1e9
 
-    copy_gbps = probe(lambda: _hip.check(lib.ofmk_hbm_copy(probe_src.data_ptr(), probe_dst.data_ptr(), nbytes, s)), 2 * nbytes)
-    read_gbps = probe(lambda: _hip.check(lib.ofmk_hbm_read(probe_src.data_ptr(), nbytes, sink.data_ptr(), s)), nbytes)
+        copy_gbps = probe(lambda: _hip.check(lib.ofmk_hbm_copy(probe_src.data_ptr(), probe_dst.data_ptr(), nbytes, s)), 2 * nbytes)
+        read_gbps = probe(lambda: _hip.check(lib.ofmk_hbm_read(probe_src.data_ptr(), nbytes, sink.data_ptr(), s)), nbytes)
 
-    for key, ceil_name, ceil in (("embed_only", "frac_of_measured_copy", copy_gbps), ("detect_only", "frac_of_measured_read", read_gbps)):
-        if key in extra and "algorithmic_GBps" in extra[key]:
-            extra[key][ceil_name] = round(extra[key]["algorithmic_GBps"] / (ceil * world), 4)
+        for key, ceil_name, ceil in (("embed_only", "frac_of_measured_copy", copy_gbps), ("detect_only", "frac_of_measured_read", read_gbps)):
+            if key in extra and "algorithmic_GBps" in extra[key]:
+                extra[key][ceil_name] = round(extra[key]["algorithmic_GBps"] / (ceil * world), 4)
     units = n if emu else job.total_frames                  # emulation: `value` is what this ONE GPU really processed
     fps = units * a.steps / elapsed
     frame_bytes = 3 * H * W
@@ -1422,8 +1487,8 @@ def main():
         "roofline": roof,
         "path": {"algorithmic_GBps": round(path_gbps, 1), "bytes_per_frame": bpp * H * W,
                  "frac_of_peak": round(path_gbps / (HBM_PEAK_GBPS * world), 4),
-                 "frac_of_measured_copy": round(path_gbps / (copy_gbps * world), 4)},
-        "hbm_copy_GBps": round(copy_gbps, 1), "hbm_read_GBps": round(read_gbps, 1),
+                 "frac_of_measured_copy": round(path_gbps / (copy_gbps * world), 4) if copy_gbps else None},
+        "hbm_copy_GBps": round(copy_gbps, 1) if copy_gbps else None, "hbm_read_GBps": round(read_gbps, 1) if read_gbps else None,
         "source_sha16": sha,
         "collective": {"backend": ("rccl" if a.backend == "nccl" else a.backend) if grouped else None, "ranks": ranks_seen,
                        "self_launched": bool(os.environ.get("OFMK_BENCH_SELF_LAUNCHED")), "env": rank_env},
@@ -1470,6 +1535,8 @@ def main():
                                                                      [job.wm_table[int(r)] for r in rows_sel], pay_svd, blk_)
             except Exception as exc:
                 line["oracle_check"] = dict(error=repr(exc))
+    if dump is not None:
+        write_outputs(a.dump_outputs, dump)
     print(json.dumps(line), flush=True)
 
 

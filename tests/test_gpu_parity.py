@@ -1108,7 +1108,7 @@ def test_bench_dry_run_of_the_collective_path():
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--rehearse-collectives", "--frames", "8",
-                        "--height", "240", "--width", "320", "--steps", "3", "--warmup", "1", "--no-cpu-baseline"],
+                        "--height", "240", "--width", "320", "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline"],
                        capture_output=True, text=True, timeout=600, env=env, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
     assert len(r.stdout.strip().splitlines()) == 1, r.stdout[:400]        # ONE line on stdout: RCCL's version banner goes to stderr
@@ -1134,7 +1134,7 @@ def test_bench_configs_run_at_one_gpu(config, extra):
     if config in (4, 5):
         small += ["--frames", "6"]
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--config", str(config), "--steps", "3", "--warmup", "1",
-                        "--no-cpu-baseline", *small, *extra], capture_output=True, text=True, timeout=900, env=env, cwd=root)
+                        "--full", "--no-cpu-baseline", *small, *extra], capture_output=True, text=True, timeout=900, env=env, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])
     assert line["payload_bit_exact"] and line["n_gpus"] == 1 and line["value"] > 0
@@ -1171,6 +1171,50 @@ def test_bench_configs_run_at_one_gpu(config, extra):
         assert line["pcie_inclusive"]["i420"]["frames_per_s"] > 0 and line["pcie_inclusive"]["rgb24"]["frames_per_s"] > 0
 
 
+@pytest.mark.parametrize("size", [["--frames", "24"], ["--height", "240", "--width", "320", "--frames", "8"]])
+def test_bench_plain_run_is_lean_and_dumps_its_last_step(tmp_path, size):
+    """A plain run (no --full) times the K steps and reports the headline only; --dump-outputs writes what the last timed step
+    computed (float32 / float64, at most 64 MB; 24 x 1080p is sampled, 8 x 320x240 written whole), and two runs with the same
+    arguments write the same arrays: the inputs are seeded."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
+    payload = np.array([0, 1, 1, 0, 0, 1, 0, 1], np.float32)
+    runs = []
+    for i in range(2):
+        out = tmp_path / f"run{i}"
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "1", *size,
+                            "--dump-outputs", str(out)], capture_output=True, text=True, timeout=600, env=env, cwd=root)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, r.stdout[-2000:]
+        line = json.loads(lines[0])
+        n = line["config"]["frames_per_gpu"]
+        assert line["payload_bit_exact"] and line["steps"] == 4 and line["warmup"] == 1 and line["n_gpus"] == 1
+        assert line["unit"] == "frames/s" and line["higher_is_better"] is True and line["dtype"] == "f32"
+        assert abs(line["value"] - n * 1e3 / line["ms_per_step"]) <= 1e-3 * line["value"]
+        for key in ("value_no_preheat", "value_second_pass", "kernels", "mark_order", "embed_only", "separate_detect", "dwtdctsvd", "oracle_check"):
+            assert key not in line, key
+        assert line["roofline"] is None and line["cpu_baseline"] is None and line["hbm_copy_GBps"] is None
+        files = sorted(out.iterdir())
+        assert sum(f.stat().st_size for f in files) <= 64 << 20
+        arrays = {f.name[:-4]: np.load(f) for f in files}
+        assert all(a_.dtype in (np.float32, np.float64) for a_ in arrays.values())
+        assert np.array_equal(arrays["payloads"], np.tile(payload, (n, 1)))
+        assert np.array_equal(arrays["vote_payloads"], payload[None]) and arrays["vote_frequencies"].tolist() == [1.0]
+        if "--height" in size:
+            marked = arrays["marked"]
+            assert marked.shape == (n, 240, 320, 3) and "marked_sample" not in arrays
+        else:
+            marked = arrays["marked_sample"]
+            assert marked.ndim == 1 and 0.9 * 2 ** 23 < marked.size <= 2 ** 23 and "marked" not in arrays
+        assert marked.min() >= 0 and marked.max() <= 255 and np.array_equal(marked, np.round(marked))
+        runs.append(arrays)
+    assert runs[0].keys() == runs[1].keys() and all(np.array_equal(runs[0][k], runs[1][k]) for k in runs[0])
+
+
 @pytest.mark.parametrize("config,size", [(2, ["--height", "360", "--width", "640", "--frames", "12"]), (4, ["--height", "240", "--width", "320", "--frames", "6"])])
 def test_bench_line_checks_its_own_timed_frames_against_the_oracle(config, size):
     """the line itself compares frames of the TIMED batch and the marked frames the timed steps wrote with
@@ -1183,7 +1227,7 @@ def test_bench_line_checks_its_own_timed_frames_against_the_oracle(config, size)
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--config", str(config), "--steps", "3", "--warmup", "1",
-                        "--cpu-seconds", "1", *size], capture_output=True, text=True, timeout=900, env=env, cwd=root)
+                        "--full", "--cpu-seconds", "1", *size], capture_output=True, text=True, timeout=900, env=env, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])
     oc = line["oracle_check"]
@@ -1216,7 +1260,7 @@ def test_bench_config3_4k_at_its_stated_size():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--config", "3", "--steps", "3", "--warmup", "1",
-                        "--no-cpu-baseline"], capture_output=True, text=True, timeout=1500, env=env, cwd=root)
+                        "--full", "--no-cpu-baseline"], capture_output=True, text=True, timeout=1500, env=env, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])
     assert line["payload_bit_exact"] and line["second_pass"]["votes_ok"] and line["config"]["frames_per_gpu"] == 1000
@@ -1243,7 +1287,7 @@ def test_bench_emulates_rank_0_of_an_8_rank_job(config, extra):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--config", str(config), "--emulate-world", "8", "--steps", "20",
-                        "--warmup", "5", "--no-cpu-baseline", *extra], capture_output=True, text=True, timeout=900, env=env, cwd=root)
+                        "--warmup", "5", "--full", "--no-cpu-baseline", *extra], capture_output=True, text=True, timeout=900, env=env, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])
     em = line["emulation"]
@@ -1279,7 +1323,7 @@ def test_bench_two_ranks_gloo_on_one_device(config, launcher):
                  "--master-port", str(port)]
     cmd = head + [os.path.join(root, "bench.py"), "--gpus", "2", "--backend", "gloo", "--single-device",
                   "--config", str(config), "--height", "240", "--width", "320", "--frames", "8", "--steps", "3", "--warmup", "1",
-                  "--no-cpu-baseline"] + (["--no-extras"] if config != 2 else ["--side-measurements"])      # config 2: the side measurements run on every rank too
+                  "--full", "--no-cpu-baseline"] + (["--no-extras"] if config != 2 else ["--side-measurements"])      # config 2: the side measurements run on every rank too
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=root)
     assert r.returncode == 0, r.stderr[-3000:]
     out_lines = [l for l in r.stdout.strip().splitlines() if l.startswith("{")]
@@ -1314,7 +1358,7 @@ def test_bench_rank_without_a_shard_stays_in_step_with_its_peers():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "3", "--backend", "gloo", "--single-device", "--config", "4",
                         "--segments", "2", "--height", "240", "--width", "320", "--frames", "8", "--steps", "4", "--warmup", "1",
-                        "--preheat-ms", "40", "--no-cpu-baseline"], capture_output=True, text=True, timeout=600, env=env, cwd=root)
+                        "--preheat-ms", "40", "--full", "--no-cpu-baseline"], capture_output=True, text=True, timeout=600, env=env, cwd=root)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert line["n_gpus"] == 3 and line["payload_bit_exact"] and line["config"]["preheat_ms"] > 0
@@ -1335,7 +1379,7 @@ def test_bench_rank_failure_ends_the_whole_job(where, flags):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     args = ["--backend", "gloo", "--single-device", "--height", "240", "--width", "320", "--frames", "8", "--steps", "3", "--warmup", "1",
-            "--no-cpu-baseline", *flags]
+            "--full", "--no-cpu-baseline", *flags]
     t0 = time.perf_counter()
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", *args], capture_output=True, text=True, timeout=300,
                        env=dict(env, OFMK_BENCH_INJECT_FAILURE=f"1:{where}"), cwd=root)
@@ -1344,7 +1388,7 @@ def test_bench_rank_failure_ends_the_whole_job(where, flags):
     assert not [l for l in r.stdout.splitlines() if l.startswith("{")], r.stdout[-500:]
     assert f"injected failure in rank 1 at {where}" in r.stderr
     if where == "second_pass":          # the healthy twin, and the one-GPU run of the same arguments, at a size where the work (not the interpreter start-up) sets the time
-        big = ["--backend", "gloo", "--single-device", "--frames", "60", "--steps", "10", "--warmup", "2", "--no-cpu-baseline"]
+        big = ["--backend", "gloo", "--single-device", "--frames", "60", "--steps", "10", "--warmup", "2", "--full", "--no-cpu-baseline"]
         t0 = time.perf_counter()
         ok2 = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", *big], capture_output=True, text=True,
                              timeout=600, env=env, cwd=root)

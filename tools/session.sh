@@ -13,14 +13,14 @@ run() {   # run <seconds> <name> <command...>: stdout -> $O/${TAG}_<name>.json|l
     if [ $rc -ge 124 ]; then echo "step $name was killed: stopping the session"; exit $rc; fi
     return 0
 }
-B="python bench.py --no-cpu-baseline"
+B="python bench.py --full --no-cpu-baseline"
 for step in "$@"; do
   case $step in
     tests)     AMD_LOG_LEVEL=1 run 1100 tests python -X faulthandler -m pytest tests -m gpu -v -x --capture=sys; tail -5 $O/${TAG}_tests.out; grep -v "^  File\|amdgpu.ids" $O/${TAG}_tests.err | head -20 ;;
     tests_all) AMD_LOG_LEVEL=1 run 1100 tests python -X faulthandler -m pytest tests -m gpu -v --capture=sys; tail -30 $O/${TAG}_tests.out | grep -v PASSED; grep -v "^  File\|amdgpu.ids" $O/${TAG}_tests.err | head -20 ;;
     memset)    run 200 graph_memset_order python tools/graph_memset_order.py; cat $O/${TAG}_graph_memset_order.out ;;
-    line)      run 400 bench_line python bench.py ;;
-    line20)    run 400 bench_line_steps20_warmup5 python bench.py --steps 20 --warmup 5 ;;
+    line)      run 400 bench_line python bench.py --full ;;
+    line20)    run 400 bench_line_steps20_warmup5 python bench.py --full --steps 20 --warmup 5 ;;
     c3)        run 600 bench_config3_4k_1000frames $B --config 3 --steps 20 --warmup 3 ;;
     c4)        run 300 bench_config4 $B --config 4 ;;
     c5)        run 300 bench_config5 $B --config 5 ;;

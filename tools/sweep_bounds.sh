@@ -4,6 +4,7 @@
 set -e
 SRC=video-fingerprinting_amd/csrc/offmark_kernels.hip
 LIB=video-fingerprinting_amd/offmark/_lib/liboffmark_hip.so
+BENCH_ARGS="--full $BENCH_ARGS"          # every measurement: tools/show_sweep.py reads the per-kernel and side figures
 cp $LIB /tmp/lib_orig.so
 for cfg in "$@"; do
   hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fno-slp-vectorize -fPIC -shared $cfg $SRC -o $LIB
