@@ -187,6 +187,28 @@ int ofmk_embed_detect_yuv420(const uint8_t *in, uint8_t *out, int layout, int n,
                              const uint8_t *wm, int n_wm, const int32_t *wm_row, double alpha,
                              int L, int32_t *counts, uint8_t *bits,
                              int chunk_frames, void *workspace, size_t workspace_bytes, void *stream, const ofmk_opts *opts);
+/* The DwtDctSvd codec on the same 4:2:0 planes.  `scales`, `blk`, `wm` / `n_wm` / `wm_row`, `L` / `counts` / `bits` and `opts`
+ * (OFMK_F_PARTIAL_COUNTS included: tiles = ofmk_svd_count_tiles(H, W, blk)) as ofmk_svd_*_rgb8; `layout` and the planes as
+ * ofmk_*_yuv420 above; no workspace.  The result is, bit for bit,
+ *     ofmk_svd_embed_yuv420         == ofmk_rgb8_to_yuv420(ofmk_svd_embed_rgb8(ofmk_yuv420_to_rgb8(in)))
+ *     ofmk_svd_detect_yuv420        == ofmk_svd_detect_rgb8(ofmk_yuv420_to_rgb8(in))
+ *     ofmk_svd_embed_detect_yuv420  == `out` as the embed; counts / bits == ofmk_svd_detect_yuv420(out), what a reader of the
+ *                                      WRITTEN planes sees (the verify reads out with the stand-alone read-out's tolerance)
+ * in one tile-local pass: 1.5 B/px read and 1.5 B/px written instead of the chain's 15 B/px (embed) and 7.5 B/px (detect).
+ *   blk = 8  the tiles cover only the first 16*floor(H/16) rows and 16*floor(W/16) columns; the pixels outside come out as the
+ *            chain leaves them: the planes -> RGB -> planes round trip of the input (not the input bytes), also when in == out
+ *            (one more launch, timed as "svd" like the tile launch).  `bits` is [n][H*W/256]; entries past the tiles are 0.
+ *   blk = 4  `bits` is [n][H*W/64]; with H and W multiples of 8 there is no fringe.
+ *   in == out is allowed.  Arguments are checked before any HIP call (OFMK_E_ARG): as the rgb8 SVD calls, plus the layout, H and W
+ *   multiples of 8 and 8-byte aligned frame buffers. */
+int ofmk_svd_embed_yuv420(const uint8_t *in, uint8_t *out, int layout, int n, int H, int W,
+                          const uint8_t *wm, int n_wm, const int32_t *wm_row, const double *scales, int blk,
+                          void *stream, const ofmk_opts *opts);
+int ofmk_svd_detect_yuv420(const uint8_t *in, int layout, int n, int H, int W, int L, const double *scales, int blk,
+                           int32_t *counts, uint8_t *bits, void *stream, const ofmk_opts *opts);
+int ofmk_svd_embed_detect_yuv420(const uint8_t *in, uint8_t *out, int layout, int n, int H, int W,
+                                 const uint8_t *wm, int n_wm, const int32_t *wm_row, const double *scales, int blk,
+                                 int L, int32_t *counts, uint8_t *bits, void *stream, const ofmk_opts *opts);
 int ofmk_yuv420_to_rgb8(const uint8_t *yuv, uint8_t *rgb, int layout, int n, int H, int W, void *stream,
                         const ofmk_opts *opts);
 int ofmk_rgb8_to_yuv420(const uint8_t *rgb, uint8_t *yuv, int layout, int n, int H, int W, void *stream,

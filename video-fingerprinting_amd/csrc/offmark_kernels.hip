@@ -43,6 +43,7 @@
 #include "svd8_kernels.hiph"
 #include "misc_kernels.hiph"
 #include "planar_kernels.hiph"
+#include "svd_planar_kernels.hiph"
 
 namespace {
 
@@ -566,6 +567,95 @@ int launch_mark_yuv420(const uint8_t *in, uint8_t *out, int layout, int n, int H
     return OFMK_OK;
 }
 
+// ---- DwtDctSvd codec on planar YUV 4:2:0 (svd_planar_kernels.hiph) --------------------------------------------------
+// The same grid as launch_svd_rgb8 / launch_svd8_rgb8 (one thread per tile, kThreads per workgroup, linear order), so partial
+// counts have ofmk_svd_count_tiles(H, W, blk) rows; the same zero-fills in front; timed under KIND_SVD.
+int launch_svd_yuv420(const uint8_t *in, uint8_t *out, int layout, int n, int H, int W, int mode, SvdArgs a, const Ctx &cx) {
+    hipStream_t s = cx.s;
+    const PGeom g = make_pgeom(layout, H, W, 0);
+    const size_t tiles = (size_t)(g.nblk + kThreads - 1) / kThreads;
+    if (a.counts && !a.partial) HIP_TRY(launch_zero(a.counts, (size_t)n * a.L * sizeof(int32_t), s));
+    const bool multi = a.scales[0] > 0.f || a.scales[2] > 0.f || !(a.scales[1] > 0.f);      // anything but the default [0, s, 0]
+    for (int f0 = 0; f0 < n; f0 += kMaxChunk) {
+        const int cf = n - f0 < kMaxChunk ? n - f0 : kMaxChunk;
+        const size_t fo = (size_t)f0 * g.frame_stride;
+        SvdArgs b = a;
+        if (b.wm_row) b.wm_row += f0;
+        if (b.counts) b.counts += (size_t)f0 * a.L * (a.partial ? tiles : 1);
+        if (b.bits) b.bits += (size_t)f0 * a.N;
+        const dim3 grid = xcd_grid(g.nblk, cf);
+        ScopedTiming timing(KIND_SVD, cx);
+#define OFMK_SVDP_LAUNCH(FMT, MD, MU) OFMK_TIMED_LAUNCH(timing, (svd_yuv420_kernel<FMT, MD, MU>), grid, dim3(kThreads), 0, s, in + fo, out ? out + fo : nullptr, g, cf, b)
+#define OFMK_SVDP_MODES(FMT)                                                                        \
+        if (mode == SVD_DETECT) OFMK_SVDP_LAUNCH(FMT, SVD_DETECT, false);                           \
+        else if (mode == SVD_EMBED && !multi) OFMK_SVDP_LAUNCH(FMT, SVD_EMBED, false);              \
+        else if (mode == SVD_EMBED) OFMK_SVDP_LAUNCH(FMT, SVD_EMBED, true);                         \
+        else if (!multi) OFMK_SVDP_LAUNCH(FMT, SVD_EMBED_VERIFY, false);                            \
+        else OFMK_SVDP_LAUNCH(FMT, SVD_EMBED_VERIFY, true)
+        if (layout == OFMK_YUV_I420) { OFMK_SVDP_MODES(FMT_I420); } else { OFMK_SVDP_MODES(FMT_NV12); }
+#undef OFMK_SVDP_MODES
+#undef OFMK_SVDP_LAUNCH
+    }
+    HIP_TRY(hipGetLastError());
+    return OFMK_OK;
+}
+
+// blk = 8.  The pixels outside the tiles' Hc x Wc region come out as the chain's: the 4:2:0 round trip of the input, written by
+// one more launch (also timed under KIND_SVD) -- also in place, where the RGB path has nothing to copy.
+int launch_svd8_yuv420(const uint8_t *in, uint8_t *out, int layout, int n, int H, int W, int mode, Svd8Args a, const Ctx &cx) {
+    hipStream_t s = cx.s;
+    const PGeom g = make_pgeom(layout, H, W, 0);
+    const Geom8 g8 = make_geom8(H, W);
+    const size_t tiles = (size_t)(g8.ntile + kThreads - 1) / kThreads;
+    if (a.counts && !a.partial) HIP_TRY(launch_zero(a.counts, (size_t)n * a.L * sizeof(int32_t), s));
+    if (a.bits && a.N8 > g8.ntile) HIP_TRY(launch_zero(a.bits, (size_t)n * a.N8, s));    // entries past the tiles stay 0
+    const bool multi = a.scales[0] > 0.f || a.scales[2] > 0.f || !(a.scales[1] > 0.f);
+    if (g8.ntile > 0) {
+        for (int f0 = 0; f0 < n; f0 += kMaxChunk) {
+            const int cf = n - f0 < kMaxChunk ? n - f0 : kMaxChunk;
+            const size_t fo = (size_t)f0 * g.frame_stride;
+            Svd8Args b = a;
+            if (b.wm_row) b.wm_row += f0;
+            if (b.counts) b.counts += (size_t)f0 * a.L * (a.partial ? tiles : 1);
+            if (b.bits) b.bits += (size_t)f0 * a.N8;
+            Geom8 gc = g8;
+            gc.frames = cf;
+            const dim3 grid = xcd_grid(g8.ntile, cf);
+            ScopedTiming timing(KIND_SVD, cx);
+#define OFMK_SVD8P_LAUNCH(FMT, MD, MU) OFMK_TIMED_LAUNCH(timing, (svd8_yuv420_kernel<FMT, MD, MU>), grid, dim3(kThreads), 0, s, in + fo, out ? out + fo : nullptr, g, gc, b)
+#define OFMK_SVD8P_MODES(FMT)                                                                       \
+            if (mode == SVD_DETECT) OFMK_SVD8P_LAUNCH(FMT, SVD_DETECT, false);                      \
+            else if (mode == SVD_EMBED && !multi) OFMK_SVD8P_LAUNCH(FMT, SVD_EMBED, false);         \
+            else if (mode == SVD_EMBED) OFMK_SVD8P_LAUNCH(FMT, SVD_EMBED, true);                    \
+            else if (!multi) OFMK_SVD8P_LAUNCH(FMT, SVD_EMBED_VERIFY, false);                       \
+            else OFMK_SVD8P_LAUNCH(FMT, SVD_EMBED_VERIFY, true)
+            if (layout == OFMK_YUV_I420) { OFMK_SVD8P_MODES(FMT_I420); } else { OFMK_SVD8P_MODES(FMT_NV12); }
+#undef OFMK_SVD8P_MODES
+#undef OFMK_SVD8P_LAUNCH
+        }
+        HIP_TRY(hipGetLastError());
+    }
+    const int hcb = (((H / 4) * 2) / 8) * 2, wcb = g8.wt * 2;                 // the tiles' Hc x Wc region in 8x8 pixel blocks
+    const int nfringe = g.nblk - hcb * wcb;
+    if (mode != SVD_DETECT && nfringe > 0) {
+        for (int f0 = 0; f0 < n; f0 += kMaxChunk) {
+            const int cf = n - f0 < kMaxChunk ? n - f0 : kMaxChunk;
+            const size_t fo = (size_t)f0 * g.frame_stride;
+            const dim3 grid((unsigned)((nfringe + kThreads - 1) / kThreads), (unsigned)cf);
+            ScopedTiming timing(KIND_SVD, cx);
+            if (layout == OFMK_YUV_I420) OFMK_TIMED_LAUNCH(timing, svd_fringe_yuv420_kernel<FMT_I420>, grid, dim3(kThreads), 0, s, in + fo, out + fo, g, hcb, wcb, nfringe);
+            else OFMK_TIMED_LAUNCH(timing, svd_fringe_yuv420_kernel<FMT_NV12>, grid, dim3(kThreads), 0, s, in + fo, out + fo, g, hcb, wcb, nfringe);
+        }
+        HIP_TRY(hipGetLastError());
+    }
+    return OFMK_OK;
+}
+
+int launch_svd_planar(const uint8_t *in, uint8_t *out, int layout, int n, int H, int W, int mode, const SvdArgs &a, int blk, const Ctx &cx) {
+    if (blk == 8) return launch_svd8_yuv420(in, out, layout, n, H, W, mode, to_args8(a, H, W), cx);
+    return launch_svd_yuv420(in, out, layout, n, H, W, mode, a, cx);
+}
+
 // scales: host double[3], one per YUV channel (dwt_dct_svd_encoder.py:6: scales=[0,15,0]); <= 0 leaves a channel alone
 int set_scales(SvdArgs &a, const double *scales, bool need_channel1) {
     if (!scales) return fail(OFMK_E_ARG, "scales is null (host array of 3 doubles)%s");
@@ -985,6 +1075,62 @@ int ofmk_embed_detect_yuv420(const uint8_t *in, uint8_t *out, int layout, int n,
         }
     }
     return OFMK_OK;
+}
+
+// ---- DwtDctSvd codec on planar YUV 4:2:0: the rgb8 SVD calls' conventions, the yuv420 calls' layout ----------------------------
+int ofmk_svd_embed_yuv420(const uint8_t *in, uint8_t *out, int layout, int n, int H, int W, const uint8_t *wm, int n_wm,
+                          const int32_t *wm_row, const double *scales, int blk, void *stream, const ofmk_opts *opts) {
+    if (int orc = check_opts(opts)) return orc;
+    int rc = check_embed_args(in, out, n, H, W, wm, n_wm);
+    if (rc) return rc;
+    if ((rc = check_blk(blk))) return rc;
+    if ((rc = check_planar(layout, H, W, in, out))) return rc;
+    SvdArgs a;
+    memset(&a, 0, sizeof(a));
+    if ((rc = set_scales(a, scales, false))) return rc;
+    a.wm = wm; a.wm_row = wm_row; a.n_wm = n_wm; a.N = (int)((long long)H * W / 64); a.L = 1;
+    return launch_svd_planar(in, out, layout, n, H, W, SVD_EMBED, a, blk, make_ctx(stream, opts));
+}
+
+// scales[1] <= 0: zeroed counts / bits, as ofmk_svd_detect_rgb8
+int ofmk_svd_detect_yuv420(const uint8_t *in, int layout, int n, int H, int W, int L, const double *scales, int blk,
+                           int32_t *counts, uint8_t *bits, void *stream, const ofmk_opts *opts) {
+    if (int orc = check_opts(opts)) return orc;
+    int rc = check_detect_args(in, n, H, W, L, counts, bits);
+    if (rc) return rc;
+    if ((rc = check_blk(blk))) return rc;
+    if ((rc = check_planar(layout, H, W, in, nullptr))) return rc;
+    SvdArgs a;
+    memset(&a, 0, sizeof(a));
+    if ((rc = set_scales(a, scales, true))) return rc;
+    if ((rc = check_partial(opts, L, counts, a.partial))) return rc;
+    a.counts = counts; a.bits = bits; a.N = (int)((long long)H * W / 64); a.L = L;
+    if (!(a.scales[1] > 0.f)) {
+        hipStream_t s = static_cast<hipStream_t>(stream);
+        const size_t bits_per_frame = blk == 8 ? (size_t)((long long)H * W / 256) : (size_t)a.N;
+        if (counts) HIP_TRY(launch_zero(counts, (size_t)n * L * sizeof(int32_t) * (a.partial ? (size_t)svd_count_tiles(H, W, blk) : 1), s));
+        if (bits) HIP_TRY(launch_zero(bits, (size_t)n * bits_per_frame, s));
+        return OFMK_OK;
+    }
+    return launch_svd_planar(in, nullptr, layout, n, H, W, SVD_DETECT, a, blk, make_ctx(stream, opts));
+}
+
+int ofmk_svd_embed_detect_yuv420(const uint8_t *in, uint8_t *out, int layout, int n, int H, int W, const uint8_t *wm, int n_wm,
+                                 const int32_t *wm_row, const double *scales, int blk, int L, int32_t *counts, uint8_t *bits,
+                                 void *stream, const ofmk_opts *opts) {
+    if (int orc = check_opts(opts)) return orc;
+    int rc = check_embed_args(in, out, n, H, W, wm, n_wm);
+    if (rc) return rc;
+    if ((rc = check_blk(blk))) return rc;
+    if ((rc = check_detect_args(out, n, H, W, L, counts, bits))) return rc;
+    if ((rc = check_planar(layout, H, W, in, out))) return rc;
+    SvdArgs a;
+    memset(&a, 0, sizeof(a));
+    if ((rc = set_scales(a, scales, false))) return rc;
+    if ((rc = check_partial(opts, L, counts, a.partial))) return rc;
+    a.wm = wm; a.wm_row = wm_row; a.n_wm = n_wm; a.counts = counts; a.bits = bits;
+    a.N = (int)((long long)H * W / 64); a.L = L;
+    return launch_svd_planar(in, out, layout, n, H, W, SVD_EMBED_VERIFY, a, blk, make_ctx(stream, opts));
 }
 
 int ofmk_yuv420_to_rgb8(const uint8_t *yuv, uint8_t *rgb, int layout, int n, int H, int W, void *stream, const ofmk_opts *opts) {

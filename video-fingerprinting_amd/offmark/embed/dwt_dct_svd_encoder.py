@@ -85,3 +85,11 @@ class DwtDctSvdEncoder:
         n, h, w, _ = frames.shape
         wm = wm_table if wm_table is not None else self._device_wm(h * w // 64)
         return self.engine.svd_embed(frames, wm, scales=self._scales, wm_row=wm_rows, out=out, blk=self.blk)
+
+    def encode_planes_yuv420(self, planes, height, width, out=None, wm_rows=None, wm_table=None, layout="i420"):
+        """planes: CUDA uint8 [n, 1.5*H*W] (I420: Y|U|V per frame, NV12: Y|UV): the frame step on what a decoder produces and an
+        encoder takes, the build-defined BT.601 conversion fused into the kernels.  Returns marked planes of the same layout,
+        equal bit for bit to converting to RGB, encode_frames_u8, and converting back."""
+        wm = wm_table if wm_table is not None else self._device_wm(height * width // 64)
+        return self.engine.svd_embed_yuv420(planes, height, width, wm, scales=self._scales, wm_row=wm_rows, out=out, blk=self.blk,
+                                            layout=layout)

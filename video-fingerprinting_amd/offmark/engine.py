@@ -508,6 +508,47 @@ class DctEngine:
                                                        self._o(extra_flags=flag)))
         return out, counts, bits
 
+    # -- DwtDctSvd codec on planar 8-bit YUV 4:2:0 (one tile-local pass, the conversions fused in) -------------------
+    def svd_embed_yuv420(self, planes, H, W, wm, scale=15, wm_row=None, out=None, scales=None, blk=4, layout="i420"):
+        """Mark frames given as 4:2:0 planes [n, 1.5*H*W]; returns marked planes of the same layout.  Equal, bit for bit, to
+        rgb_to_yuv420(svd_embed(yuv420_to_rgb(planes))), blk = 8's uncovered fringe included (its 4:2:0 round trip)."""
+        n = self._check_planar(planes, H, W)
+        wm = self._wm(wm, H * W // 64)
+        rows = self._rows(wm_row, n, wm.shape[0])
+        out = self._out(out, planes)
+        _hip.check(self.lib.ofmk_svd_embed_yuv420(planes.data_ptr(), out.data_ptr(), self._layout(layout), n, H, W, wm.data_ptr(),
+                                                  wm.shape[0], _hip.ptr(rows), _hip.scales3(scale, scales), int(blk),
+                                                  _hip.current_stream(), self._o()))
+        return out
+
+    def svd_detect_yuv420(self, planes, H, W, L, scale=15, want_bits=False, scales=None, blk=4, counts=None, partial=False,
+                          layout="i420"):
+        """Read-out of 4:2:0 planes: equal to svd_detect(yuv420_to_rgb(planes)).  Returns (counts, bits or None)."""
+        t = self.torch
+        n = self._check_planar(planes, H, W)
+        counts, flag = self._svd_counts(counts, n, H, W, L, blk, partial)
+        bits = t.empty((n, self.svd_bits_per_frame(H, W, blk)), dtype=t.uint8, device=self.device) if want_bits else None
+        _hip.check(self.lib.ofmk_svd_detect_yuv420(planes.data_ptr(), self._layout(layout), n, H, W, int(L), _hip.scales3(scale, scales),
+                                                   int(blk), counts.data_ptr(), _hip.ptr(bits), _hip.current_stream(),
+                                                   self._o(extra_flags=flag)))
+        return counts, bits
+
+    def svd_embed_detect_yuv420(self, planes, H, W, wm, L, scale=15, wm_row=None, out=None, want_bits=False, scales=None, blk=4,
+                                counts=None, partial=False, layout="i420"):
+        """Mark and verify on planes; counts / bits are what a reader of the WRITTEN planes gets (== svd_detect_yuv420(out))."""
+        t = self.torch
+        n = self._check_planar(planes, H, W)
+        wm = self._wm(wm, H * W // 64)
+        rows = self._rows(wm_row, n, wm.shape[0])
+        out = self._out(out, planes)
+        counts, flag = self._svd_counts(counts, n, H, W, L, blk, partial)
+        bits = t.empty((n, self.svd_bits_per_frame(H, W, blk)), dtype=t.uint8, device=self.device) if want_bits else None
+        _hip.check(self.lib.ofmk_svd_embed_detect_yuv420(planes.data_ptr(), out.data_ptr(), self._layout(layout), n, H, W, wm.data_ptr(),
+                                                         wm.shape[0], _hip.ptr(rows), _hip.scales3(scale, scales), int(blk), int(L),
+                                                         counts.data_ptr(), _hip.ptr(bits), _hip.current_stream(),
+                                                         self._o(extra_flags=flag)))
+        return out, counts, bits
+
     def svd_encode_yuv(self, yuv, wm, scale=15, scales=None, blk=4):
         t = self.torch
         n, H, W = self._check_frames(yuv, t.float32)
