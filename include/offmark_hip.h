@@ -155,6 +155,36 @@ int ofmk_svd_detect_rgb8(const uint8_t *in, int n, int H, int W, int L, const do
 int ofmk_svd_embed_detect_rgb8(const uint8_t *in, uint8_t *out, int n, int H, int W,
                                const uint8_t *wm, int n_wm, const int32_t *wm_row, const double *scales, int blk,
                                int L, int32_t *counts, uint8_t *bits, void *stream, const ofmk_opts *opts);
+/* ---- C differently marked copies of the same frames in one pass (the A/B workflow) ----------------------------------
+ * tests/mark_video_to_hls.py:331-342 decodes every segment once per copy and marks it with payload segment(4b)||copy(4b).
+ * These calls read the frames once, do the part of the codec that does not depend on the watermark bit once (DCT: analyze's
+ * records, masks and step; DwtDctSvd: the Haar LL band and top singular triple per tile) and write every copy.
+ *   out      device u8 [copies][n][H][W][3], copy-major; must not overlap `in` (no in-place: OFMK_E_ARG)
+ *   copies   1..16 (a payload's copy field has 4 bits)
+ *   wm_rows  device int32 [copies][n]: entry [c][f] is the watermark row of frame f in copy c, clamped into [0, n_wm) as wm_row
+ *            is; NULL = copy c uses row c (clamped) for every frame
+ * Exact semantics, byte for byte:
+ *   ofmk_embed_copies_rgb8: copy c == ofmk_embed_rgb8(in, wm, n_wm, wm_rows + c*n, alpha), the fringe pixels of an H or W that is
+ *     not a multiple of 8 included (copied from `in` into every copy).  `chunk_frames` / `workspace` as ofmk_embed_rgb8: the
+ *     analysis records are shared by all copies, so ofmk_workspace_bytes(chunk, H, W) is all it needs (less than
+ *     ofmk_workspace_bytes(1, H, W): OFMK_E_WORKSPACE).  Tile-order flags as ofmk_embed_rgb8 (a permutation: same bytes).
+ *     Launches are timed as kind 2 (mark) and 0 (analyze).
+ *   ofmk_svd_embed_copies_rgb8: copy c == ofmk_svd_embed_rgb8(in, wm, n_wm, wm_rows + c*n, scales, blk).  With `counts` or
+ *     `bits` (verify; L >= 1): the counts and bits of copy c are what ofmk_svd_embed_detect_rgb8 returns for that copy (by that
+ *     function's contract, ofmk_svd_detect_rgb8 of the copy): counts [copies][n][L], or with OFMK_F_PARTIAL_COUNTS
+ *     [copies][n][tiles][L] (tiles = ofmk_svd_count_tiles(H, W, blk), L <= 2048, counts non-null); bits [copies][n][bits per frame]
+ *     (H*W/64 for blk 4, H*W/256 for blk 8).  Both NULL: no verify, L is ignored.  blk 4 runs one fused copies kernel; blk 8
+ *     runs the single-copy launches once per copy (the same results, no saving).  Launches are timed as kind 4 (svd).
+ *   With copies == 1 each call equals its single-copy counterpart; no result depends on chunk_frames, the workspace size or
+ *   the tile order.  Arguments are checked before any HIP call (OFMK_E_ARG): as the single-copy calls, plus the range of
+ *   copies and the overlap of out with in. */
+int ofmk_embed_copies_rgb8(const uint8_t *in, uint8_t *out, int copies, int n, int H, int W,
+                           const uint8_t *wm, int n_wm, const int32_t *wm_rows, double alpha,
+                           int chunk_frames, void *workspace, size_t workspace_bytes, void *stream,
+                           const ofmk_opts *opts);
+int ofmk_svd_embed_copies_rgb8(const uint8_t *in, uint8_t *out, int copies, int n, int H, int W,
+                               const uint8_t *wm, int n_wm, const int32_t *wm_rows, const double *scales, int blk,
+                               int L, int32_t *counts, uint8_t *bits, void *stream, const ofmk_opts *opts);
 /* plugin level, float32 YUV [n][H][W][3] (n <= 65535): encode mutates the marked channels; decode fills bits */
 int ofmk_svd_encode_yuv32f(float *yuv, int n, int H, int W,
                            const uint8_t *wm, int n_wm, const int32_t *wm_row, const double *scales, int blk, void *stream,

@@ -44,6 +44,7 @@
 #include "misc_kernels.hiph"
 #include "planar_kernels.hiph"
 #include "svd_planar_kernels.hiph"
+#include "copies_kernels.hiph"
 
 namespace {
 
@@ -690,6 +691,100 @@ int check_detect_args(const void *in, int n, int H, int W, int L, const int32_t 
     return OFMK_OK;
 }
 
+// ---- C marked copies of the same frames (copies_kernels.hiph) -------------------------------------------------------
+constexpr int kMaxCopies = 16;       // a payload's copy field has 4 bits (fingerprint.payload_for_segment)
+
+// The argument checks every copies call shares: copies in range, out ([copies][n][H][W][3]) not overlapping in ([n][H][W][3]).
+int check_copies(const void *in, const void *out, int copies, int n, int H, int W) {
+    if (copies < 1 || copies > kMaxCopies) return fail(OFMK_E_ARG, "copies must be in [1, 16]%s");
+    const size_t fb = (size_t)n * H * W * 3;
+    const uintptr_t i0 = (uintptr_t)in, o0 = (uintptr_t)out;
+    if (o0 < i0 + fb && i0 < o0 + fb * (size_t)copies) return fail(OFMK_E_ARG, "out must not overlap in (no in-place copies)%s");
+    return OFMK_OK;
+}
+
+// One chunk of frames [f0, f0+cf) after launch_analyze left their records in ws: every copy of them in one launch.
+int launch_mark_copies_rgb8(const uint8_t *in, uint8_t *out, int copies, int n, int f0, int cf, int H, int W, const uint8_t *wm,
+                            int n_wm, const int32_t *wm_rows, double alpha, const Workspace &ws, const Ctx &cx) {
+    const size_t fs = (size_t)H * W * 3;
+    const uint8_t *pin = in + (size_t)f0 * fs;
+    uint8_t *pout = out + (size_t)f0 * fs;
+    const int xc = tile_xcds(cx, (size_t)cf * fs);
+    const Geom g = make_geom(H, W, ws, cf, xc);
+    const dim3 grid = xcd_grid(g.nblk, cf, xc);
+    const bool al = aligned_rows(in, W, 1) && aligned_rows(out, W, 1);     // frame and copy strides are multiples of 8 when W is
+    MarkArgs m;
+    m.rec = ws.rec;
+    m.ysum = ws.ysum;
+    m.wm = wm;
+    m.wm_row = nullptr;
+    m.n_wm = n_wm;
+    m.N = (int)((long long)H * W / 64);
+    m.alpha = alpha;
+    CopyArgs k;
+    memset(&k, 0, sizeof(k));
+    k.copies = copies;
+    k.rows_stride = n;
+    k.wm_rows = wm_rows ? wm_rows + f0 : nullptr;
+    k.out_stride = (size_t)n * fs;
+    ScopedTiming timing(KIND_MARK, cx);
+    if (al) OFMK_TIMED_LAUNCH(timing, mark_copies_rgb8_kernel<true>, grid, dim3(kThreads), 0, cx.s, pin, pout, g, m, k);
+    else OFMK_TIMED_LAUNCH(timing, mark_copies_rgb8_kernel<false>, grid, dim3(kThreads), 0, cx.s, pin, pout, g, m, k);
+    HIP_TRY(hipGetLastError());
+    return OFMK_OK;
+}
+
+// blk = 4: every copy from one launch per kMaxChunk frames; counts / bits of copy q at q * (the single-copy call's size).
+int launch_svd_copies_rgb8(const uint8_t *in, uint8_t *out, int copies, int n, int H, int W, const int32_t *wm_rows, SvdArgs a,
+                           const Ctx &cx) {
+    hipStream_t s = cx.s;
+    Workspace none;
+    none.plane = 0;
+    const Geom g = make_geom(H, W, none);
+    const bool verify = a.counts || a.bits;
+    const bool al = aligned_rows(in, W, 1) && aligned_rows(out, W, 1);
+    const size_t tiles = (size_t)(g.nblk + kThreads - 1) / kThreads;
+    CopyArgs k;
+    memset(&k, 0, sizeof(k));
+    k.copies = copies;
+    k.rows_stride = n;
+    k.out_stride = (size_t)n * g.frame_stride;
+    k.counts_stride = (size_t)n * a.L * (a.partial ? tiles : 1);
+    k.bits_stride = (size_t)n * a.N;
+    if (a.counts && !a.partial) HIP_TRY(launch_zero(a.counts, (size_t)copies * k.counts_stride * sizeof(int32_t), s));
+    if (a.bits && a.N > g.nblk) HIP_TRY(launch_zero(a.bits, (size_t)copies * k.bits_stride, s));   // entries past (H/8)(W/8) stay 0
+    const bool multi = a.scales[0] > 0.f || a.scales[2] > 0.f || !(a.scales[1] > 0.f);      // anything but the default [0, s, 0]
+    for (int f0 = 0; f0 < n; f0 += kMaxChunk) {
+        const int cf = n - f0 < kMaxChunk ? n - f0 : kMaxChunk;
+        const size_t fo = (size_t)f0 * g.frame_stride;
+        SvdArgs b = a;
+        b.wm_row = nullptr;
+        if (b.counts) b.counts += (size_t)f0 * a.L * (a.partial ? tiles : 1);
+        if (b.bits) b.bits += (size_t)f0 * a.N;
+        CopyArgs kc = k;
+        kc.wm_rows = wm_rows ? wm_rows + f0 : nullptr;
+        Geom gc = g;
+        gc.frames = cf;
+        const dim3 grid = xcd_grid(g.nblk, cf);
+        ScopedTiming timing(KIND_SVD, cx);
+#define OFMK_SVDC_LAUNCH(AL, VF, MU) OFMK_TIMED_LAUNCH(timing, (svd_copies_rgb8_kernel<AL, VF, MU>), grid, dim3(kThreads), 0, s, in + fo, out + fo, gc, b, kc)
+#define OFMK_SVDC_MODES(AL)                                                                      \
+        if (!verify && !multi) OFMK_SVDC_LAUNCH(AL, false, false);                               \
+        else if (!verify) OFMK_SVDC_LAUNCH(AL, false, true);                                     \
+        else if (!multi) OFMK_SVDC_LAUNCH(AL, true, false);                                      \
+        else OFMK_SVDC_LAUNCH(AL, true, true)
+        if (al) { OFMK_SVDC_MODES(true); } else { OFMK_SVDC_MODES(false); }
+#undef OFMK_SVDC_MODES
+#undef OFMK_SVDC_LAUNCH
+    }
+    HIP_TRY(hipGetLastError());
+    if (H % 8 || W % 8) {
+        for (int q = 0; q < copies; ++q) launch_copy_fringe(in, out + (size_t)q * k.out_stride, n, H, W, (H / 8) * 8, (W / 8) * 8, s);
+        HIP_TRY(hipGetLastError());
+    }
+    return OFMK_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -913,6 +1008,67 @@ int ofmk_svd_embed_detect_rgb8(const uint8_t *in, uint8_t *out, int n, int H, in
     a.N = (int)((long long)H * W / 64); a.L = L;
     if (blk == 8) return launch_svd8_rgb8(in, out, n, H, W, SVD_EMBED_VERIFY, to_args8(a, H, W), make_ctx(stream, opts));
     return launch_svd_rgb8(in, out, n, H, W, SVD_EMBED_VERIFY, a, make_ctx(stream, opts));
+}
+
+int ofmk_embed_copies_rgb8(const uint8_t *in, uint8_t *out, int copies, int n, int H, int W, const uint8_t *wm, int n_wm,
+                           const int32_t *wm_rows, double alpha, int chunk_frames, void *workspace, size_t workspace_bytes,
+                           void *stream, const ofmk_opts *opts) {
+    if (int orc = check_opts(opts)) return orc;
+    int rc = check_embed_args(in, out, n, H, W, wm, n_wm);
+    if (rc) return rc;
+    if ((rc = check_copies(in, out, copies, n, H, W))) return rc;
+    Workspace ws;
+    if ((rc = carve(workspace, workspace_bytes, H, W, chunk_frames, ws))) return rc;
+    const Ctx cx = make_ctx(stream, opts);
+    const size_t fs = (size_t)H * W * 3;
+    for (int f0 = 0; f0 < n; f0 += ws.frames) {      // one analysis per chunk serves every copy
+        const int cf = n - f0 < ws.frames ? n - f0 : ws.frames;
+        if ((rc = launch_analyze(in + (size_t)f0 * fs, SRC_RGB8, cf, H, W, ws, cx))) return rc;
+        if ((rc = launch_mark_copies_rgb8(in, out, copies, n, f0, cf, H, W, wm, n_wm, wm_rows, alpha, ws, cx))) return rc;
+    }
+    if (H % 8 || W % 8) {
+        for (int q = 0; q < copies; ++q) launch_copy_fringe(in, out + (size_t)q * n * fs, n, H, W, (H / 8) * 8, (W / 8) * 8, cx.s);
+        HIP_TRY(hipGetLastError());
+    }
+    return OFMK_OK;
+}
+
+int ofmk_svd_embed_copies_rgb8(const uint8_t *in, uint8_t *out, int copies, int n, int H, int W, const uint8_t *wm, int n_wm,
+                               const int32_t *wm_rows, const double *scales, int blk, int L, int32_t *counts, uint8_t *bits,
+                               void *stream, const ofmk_opts *opts) {
+    if (int orc = check_opts(opts)) return orc;
+    int rc = check_embed_args(in, out, n, H, W, wm, n_wm);
+    if (rc) return rc;
+    if ((rc = check_copies(in, out, copies, n, H, W))) return rc;
+    if ((rc = check_blk(blk))) return rc;
+    SvdArgs a;
+    memset(&a, 0, sizeof(a));
+    if ((rc = set_scales(a, scales, false))) return rc;
+    const bool verify = counts || bits;
+    if (verify && L < 1) return fail(OFMK_E_ARG, "payload length L must be >= 1%s");
+    if ((rc = check_partial(opts, L, counts, a.partial))) return rc;
+    a.wm = wm; a.n_wm = n_wm; a.counts = counts; a.bits = bits;
+    a.N = (int)((long long)H * W / 64); a.L = verify ? L : 1;
+    const Ctx cx = make_ctx(stream, opts);
+    if (blk == 4) return launch_svd_copies_rgb8(in, out, copies, n, H, W, wm_rows, a, cx);
+    // blk = 8: the single-copy launches once per copy (no fused copies kernel for 16x16 tiles)
+    const size_t fs = (size_t)H * W * 3;
+    const size_t count_rows = a.partial ? (size_t)svd_count_tiles(H, W, 8) : 1;
+    const size_t bits8 = (size_t)((long long)H * W / 256);
+    for (int q = 0; q < copies; ++q) {
+        SvdArgs b = a;
+        if (wm_rows) {
+            b.wm_row = wm_rows + (size_t)q * n;
+        } else {                                      // row q (clamped) for every frame: that row as a one-row table
+            b.wm = wm + (size_t)(q < n_wm - 1 ? q : n_wm - 1) * a.N;
+            b.n_wm = 1;
+        }
+        if (b.counts) b.counts += (size_t)q * n * a.L * count_rows;
+        if (b.bits) b.bits += (size_t)q * n * bits8;
+        if ((rc = launch_svd8_rgb8(in, out + (size_t)q * n * fs, n, H, W, verify ? SVD_EMBED_VERIFY : SVD_EMBED, to_args8(b, H, W), cx)))
+            return rc;
+    }
+    return OFMK_OK;
 }
 
 int ofmk_svd_encode_yuv32f(float *yuv, int n, int H, int W, const uint8_t *wm, int n_wm, const int32_t *wm_row,

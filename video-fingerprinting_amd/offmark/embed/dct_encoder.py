@@ -82,6 +82,12 @@ class DctEncoder:
         wm = wm_table if wm_table is not None else self._device_wm(h * w // 64)
         return self.engine.embed(frames, wm, alpha=self.alpha, wm_row=wm_rows, out=out)
 
+    def encode_copies_u8(self, frames, wm_rows, wm_table, out=None):
+        """frames: CUDA uint8 [n, H, W, 3]; wm_rows: [C, n] rows of ``wm_table`` per copy and frame.  Returns the C marked copies
+        [C, n, H, W, 3] in one pass (the frames are read and analyzed once); copy c equals
+        encode_frames_u8(frames, wm_rows=wm_rows[c], wm_table=wm_table) byte for byte."""
+        return self.engine.embed_copies(frames, wm_table, wm_rows, alpha=self.alpha, out=out)
+
     def encode_planes_yuv420(self, planes, height, width, out=None, wm_rows=None, wm_table=None, layout="i420"):
         """planes: CUDA uint8 [n, 1.5*H*W] (I420: Y|U|V per frame, NV12: Y|UV): the frame step on what a decoder produces
         and an encoder takes (reference: ffmpeg's rgb24 pipe and yuv420p writer, frame_reader.py:42-64, frame_writer.py:33-34),

@@ -86,6 +86,20 @@ class DwtDctSvdEncoder:
         wm = wm_table if wm_table is not None else self._device_wm(h * w // 64)
         return self.engine.svd_embed(frames, wm, scales=self._scales, wm_row=wm_rows, out=out, blk=self.blk)
 
+    def encode_copies_u8(self, frames, wm_rows, wm_table, out=None):
+        """frames: CUDA uint8 [n, H, W, 3]; wm_rows: [C, n] rows of ``wm_table`` per copy and frame.  Returns the C marked copies
+        [C, n, H, W, 3] in one pass (one LL band and SVD per tile serve every copy); copy c equals
+        encode_frames_u8(frames, wm_rows=wm_rows[c], wm_table=wm_table) byte for byte."""
+        return self.engine.svd_embed_copies(frames, wm_table, wm_rows, scales=self._scales, blk=self.blk, out=out)
+
+    def encode_verify_copies_u8(self, frames, wm_rows, wm_table, payload_len, out=None):
+        """encode_copies_u8 plus the read-out of every written copy with this encoder's channel-1 scale and blk: returns
+        (copies [C, n, H, W, 3], counts int32 [C, n, payload_len]); counts[c] equals what a DwtDctSvdDecoder with the same
+        channel-1 scale and blk returns from decode_frames_u8(copies[c], payload_len)."""
+        out, counts, _ = self.engine.svd_embed_copies(frames, wm_table, wm_rows, scales=self._scales, blk=self.blk, out=out,
+                                                      L=int(payload_len))
+        return out, counts
+
     def encode_planes_yuv420(self, planes, height, width, out=None, wm_rows=None, wm_table=None, layout="i420"):
         """planes: CUDA uint8 [n, 1.5*H*W] (I420: Y|U|V per frame, NV12: Y|UV): the frame step on what a decoder produces and an
         encoder takes, the build-defined BT.601 conversion fused into the kernels.  Returns marked planes of the same layout,

@@ -508,6 +508,85 @@ class DctEngine:
                                                        self._o(extra_flags=flag)))
         return out, counts, bits
 
+    # -- C marked copies of the same frames in one pass (the A/B workflow) ----------------------------------------------
+    _MAX_COPIES = 16              # a payload's copy field has 4 bits (fingerprint.payload_for_segment)
+
+    def _copy_rows(self, wm_rows, n, n_wm, copies=None):
+        """Watermark rows of the copies -> (device int32 [C, n] or None, C).  ``wm_rows`` None: copy c uses row c, C =
+        ``copies`` (default: every row of the table).  Host arrays are range-checked as _rows checks them; device tensors when
+        ``debug_checks`` is set (the kernels clamp every entry into [0, n_wm) either way)."""
+        t = self.torch
+        if wm_rows is None:
+            C = n_wm if copies is None else int(copies)
+        else:
+            if isinstance(wm_rows, (list, tuple)):
+                wm_rows = np.asarray(wm_rows)
+            if wm_rows.ndim != 2 or wm_rows.shape[1] != n or (copies is not None and wm_rows.shape[0] != copies):
+                raise ValueError(f"wm_rows must be [copies, {n}] (one row per frame and copy); got {tuple(wm_rows.shape)}")
+            C = int(wm_rows.shape[0])
+            if isinstance(wm_rows, np.ndarray):
+                if wm_rows.size and (wm_rows.min() < 0 or wm_rows.max() >= n_wm):
+                    raise ValueError(f"wm_rows entries must be in [0, {n_wm}); got [{wm_rows.min()}, {wm_rows.max()}]")
+                wm_rows = t.from_numpy(np.ascontiguousarray(wm_rows).astype(np.int32))
+            elif (not wm_rows.is_cuda or self.debug_checks) and wm_rows.numel() and (
+                    int(wm_rows.min()) < 0 or int(wm_rows.max()) >= n_wm):
+                raise ValueError(f"wm_rows entries must be in [0, {n_wm}); got [{int(wm_rows.min())}, {int(wm_rows.max())}]")
+            wm_rows = wm_rows.to(device=self.device, dtype=t.int32).contiguous()
+        if not 1 <= C <= self._MAX_COPIES:
+            raise ValueError(f"copies must be in [1, {self._MAX_COPIES}]; got {C}")
+        return wm_rows, C
+
+    def embed_copies(self, frames, wm, wm_rows, alpha=20, out=None, copies=None):
+        """C differently marked copies of the same frames in one pass: uint8 [C, n, H, W, 3] whose copy c equals, byte for byte,
+        ``embed(frames, wm, alpha, wm_row=wm_rows[c])``.  wm_rows: [C, n] rows of ``wm`` per copy and frame, or None (copy c uses
+        row c; C = ``copies``, default the number of rows).  The analysis of the frames is done once for all copies."""
+        t = self.torch
+        n, H, W = self._check_frames(frames, t.uint8)
+        wm = self._wm(wm, H * W // 64)
+        rows, C = self._copy_rows(wm_rows, n, wm.shape[0], copies)
+        out = self._out(out, frames, (C, n, H, W, 3))
+        cf = self._chunk(n, H, W)
+        ws = self.workspace(H, W, cf)
+        stream = _hip.current_stream()
+
+        def launch(o):
+            _hip.check(self.lib.ofmk_embed_copies_rgb8(frames.data_ptr(), out.data_ptr(), C, n, H, W, wm.data_ptr(), wm.shape[0],
+                                                       _hip.ptr(rows), float(alpha), cf, ws.data_ptr(), ws.numel(), stream, o))
+        self._launch_marking(launch, frames, out, min(cf, n) * H * W * 3, False, chunks=-(-n // cf))
+        return out
+
+    def svd_embed_copies(self, frames, wm, wm_rows, scale=15, scales=None, blk=4, out=None, L=None, want_bits=False, counts=None,
+                         partial=False, copies=None):
+        """The DwtDctSvd codec's copies in one pass: copy c of the uint8 [C, n, H, W, 3] result equals ``svd_embed`` with
+        ``wm_row=wm_rows[c]``.  With ``L``: also the verify of every copy, returns (out, counts [C, n, L] -- or, ``partial``,
+        [C, n, tiles, L] -- and bits [C, n, bits_per_frame] or None), each copy's equal to ``svd_embed_detect``'s."""
+        t = self.torch
+        n, H, W = self._check_frames(frames, t.uint8)
+        wm = self._wm(wm, H * W // 64)
+        rows, C = self._copy_rows(wm_rows, n, wm.shape[0], copies)
+        out = self._out(out, frames, (C, n, H, W, 3))
+        flag, bits = 0, None
+        if L is not None:
+            if partial:
+                tiles = int(self.lib.ofmk_svd_count_tiles(H, W, int(blk)))
+                if tiles < 0:
+                    raise _hip.HipError(f"bad frame size or blk ({H}x{W}, blk={blk})")
+                shape, flag = (C, n, tiles, int(L)), _hip.F_PARTIAL_COUNTS
+            else:
+                shape = (C, n, int(L))
+            if counts is None:
+                counts = t.empty(shape, dtype=t.int32, device=self.device)
+            elif not (isinstance(counts, t.Tensor) and counts.is_cuda and counts.device == self.device and counts.dtype == t.int32
+                      and tuple(counts.shape) == shape and counts.is_contiguous()):
+                raise ValueError(f"counts must be a contiguous CUDA int32 tensor of shape {shape} on {self.device}")
+            if want_bits:
+                bits = t.empty((C, n, self.svd_bits_per_frame(H, W, blk)), dtype=t.uint8, device=self.device)
+        _hip.check(self.lib.ofmk_svd_embed_copies_rgb8(frames.data_ptr(), out.data_ptr(), C, n, H, W, wm.data_ptr(), wm.shape[0],
+                                                       _hip.ptr(rows), _hip.scales3(scale, scales), int(blk),
+                                                       int(L) if L is not None else 0, _hip.ptr(counts) if L is not None else None,
+                                                       _hip.ptr(bits), _hip.current_stream(), self._o(extra_flags=flag)))
+        return out if L is None else (out, counts, bits)
+
     # -- DwtDctSvd codec on planar 8-bit YUV 4:2:0 (one tile-local pass, the conversions fused in) -------------------
     def svd_embed_yuv420(self, planes, H, W, wm, scale=15, wm_row=None, out=None, scales=None, blk=4, layout="i420"):
         """Mark frames given as 4:2:0 planes [n, 1.5*H*W]; returns marked planes of the same layout.  Equal, bit for bit, to

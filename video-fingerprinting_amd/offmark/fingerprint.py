@@ -83,8 +83,17 @@ def identify_copies(segment_votes: dict, segment_numbers=None) -> list[int | Non
 
 # ---------------------------------------------------------------------------------------------
 # Marking N copies per segment, verifying them, and the reference's JSON sidecars
-# (tests/mark_video_to_hls.py:330-434).  The pixel work is one batched GPU call per copy.
+# (tests/mark_video_to_hls.py:330-434).  The pixel work is one batched GPU call for all copies when the encoder offers
+# encode_copies_u8, else one per copy.
 # ---------------------------------------------------------------------------------------------
+
+def _reads_like(encoder, decoder) -> bool:
+    """True when ``decoder`` reads exactly what the encoder's own verify reads: a DwtDctSvdDecoder with the encoder's channel-1
+    scale and blk (the DwtDctSvd read-out is channel 1's, dwt_dct_svd_decoder.py:24)."""
+    from .extract.dwt_dct_svd_decoder import DwtDctSvdDecoder
+    return (isinstance(decoder, DwtDctSvdDecoder) and getattr(encoder, "blk", None) == decoder.blk
+            and getattr(encoder, "_scales", [None] * 3)[1] == decoder._scales[1])
+
 
 def mark_segment_copies(encoder, decoder, frames, segment_of_frame, num_copies: int, key=0, min_frequency: float = 0.5):
     """Mark ``num_copies`` versions of every segment and verify each one.
@@ -94,7 +103,10 @@ def mark_segment_copies(encoder, decoder, frames, segment_of_frame, num_copies: 
     Returns (copies, sidecars): copies[c] is the marked tensor of copy c; sidecars holds the dicts the
     reference writes as segment_payloads.json / segment_copies.json / failed_segments.json, with the same
     keys.  A copy fails verification when its per-segment vote differs from its payload or the winning
-    pattern covers fewer than ``min_frequency`` of the frames (mark_video_to_hls.py:381)."""
+    pattern covers fewer than ``min_frequency`` of the frames (mark_video_to_hls.py:381).
+    An encoder offering ``encode_copies_u8`` marks all copies (up to 16) in one pass, and copies[c] are views of its result;
+    a DwtDctSvdEncoder whose decoder reads with the same channel-1 scale and blk also hands over the verify's counts
+    (``encode_verify_copies_u8``).  Copies and sidecars are the same either way."""
     import torch
     from .degenerator.de_shuffler import DeShuffler
     from .dist.vote import vote_segments
@@ -111,11 +123,22 @@ def mark_segment_copies(encoder, decoder, frames, segment_of_frame, num_copies: 
     table_dev = torch.from_numpy(table.astype(np.uint8)).to(frames.device)
     copies, segment_payloads, failed = [], {}, []
     segment_copies = {str(s): [] for s in segments}
+    n_bits = decoder.bits_per_frame(H, W) if hasattr(decoder, "bits_per_frame") else N      # DwtDctSvd(blk=8): H*W//256
+    rows_all = np.array([[index[(int(s), c)] for s in seg] for c in range(num_copies)], dtype=np.int32).reshape(num_copies, n)
+    marked_all = counts_all = None
+    if hasattr(encoder, "encode_copies_u8") and 1 <= num_copies <= 16:
+        # one pass for every copy: the frames are read and analyzed once (csrc/copies_kernels.hiph)
+        rows_dev = torch.from_numpy(rows_all).to(frames.device)
+        if hasattr(encoder, "encode_verify_copies_u8") and _reads_like(encoder, decoder):
+            marked_all, counts_all = encoder.encode_verify_copies_u8(frames, rows_dev, table_dev, 8)
+        else:
+            marked_all = encoder.encode_copies_u8(frames, rows_dev, table_dev)
     for c in range(num_copies):
-        rows = np.array([index[(int(s), c)] for s in seg], dtype=np.int32)
-        marked = encoder.encode_frames_u8(frames, wm_rows=torch.from_numpy(rows).to(frames.device), wm_table=table_dev)
-        counts, _ = decoder.decode_frames_u8(marked, 8)
-        n_bits = decoder.bits_per_frame(H, W) if hasattr(decoder, "bits_per_frame") else N      # DwtDctSvd(blk=8): H*W//256
+        if marked_all is not None:
+            marked = marked_all[c]
+        else:
+            marked = encoder.encode_frames_u8(frames, wm_rows=torch.from_numpy(rows_all[c]).to(frames.device), wm_table=table_dev)
+        counts = counts_all[c] if counts_all is not None else decoder.decode_frames_u8(marked, 8)[0]
         votes = vote_segments(deg.degenerate_counts(counts.cpu().numpy(), n_bits), seg)
         copies.append(marked)
         for s in segments:
