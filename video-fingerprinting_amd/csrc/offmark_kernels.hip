@@ -33,6 +33,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
+#include <type_traits>
 
 #include "../../include/offmark_hip.h"
 
@@ -150,6 +151,35 @@ hipError_t launch_zero(void *p, size_t bytes, hipStream_t s) {
 
 constexpr int kMaxChunk = 65535;   // frames per launch = gridDim.y
 
+// Frames [0, n) in chunks of at most cap (a workspace's capacity, or kMaxChunk): body(f0, cf) for frames [f0, f0 + cf), until
+// one returns an error code.
+template <class Body>
+int for_chunks(int n, int cap, Body &&body) {
+    for (int f0 = 0; f0 < n; f0 += cap)
+        if (int rc = body(f0, n - f0 < cap ? n - f0 : cap)) return rc;
+    return OFMK_OK;
+}
+
+// Runtime flag -> template argument: f is a generic lambda that receives the value as a std::integral_constant and names the kernel
+// instantiation with decltype(arg)::value.  Only the combinations a call site spells out get instantiated.
+template <class F>
+void with_bool(bool b, F &&f) {
+    if (b) f(std::true_type{});
+    else f(std::false_type{});
+}
+template <class F>
+void with_fmt(int layout, F &&f) {       // OFMK_YUV_I420 / OFMK_YUV_NV12 -> FMT_I420 / FMT_NV12 (planar_kernels.hiph)
+    if (layout == OFMK_YUV_I420) f(std::integral_constant<int, FMT_I420>{});
+    else f(std::integral_constant<int, FMT_NV12>{});
+}
+// f(mode, multi) of the DwtDctSvd frame kernels; the read-out alone has no MULTI = true form.
+template <class F>
+void with_svd_mode(int mode, bool multi, F &&f) {
+    if (mode == SVD_DETECT) f(std::integral_constant<int, SVD_DETECT>{}, std::false_type{});
+    else if (mode == SVD_EMBED) with_bool(multi, [&](auto mu) { f(std::integral_constant<int, SVD_EMBED>{}, mu); });
+    else with_bool(multi, [&](auto mu) { f(std::integral_constant<int, SVD_EMBED_VERIFY>{}, mu); });
+}
+
 struct Workspace {
     float *rec;      // kRec planes of [frames][nblk]
     float *delta;    // [frames][nblk]
@@ -208,6 +238,23 @@ int check_dims(int n, int H, int W) {
     return OFMK_OK;
 }
 
+int check_embed_args(const void *in, const void *out, int n, int H, int W, const uint8_t *wm, int n_wm) {
+    int rc = check_dims(n, H, W);
+    if (rc) return rc;
+    if (!in || !out || !wm) return fail(OFMK_E_ARG, "null frame or watermark pointer%s");
+    if (n_wm < 1) return fail(OFMK_E_ARG, "n_wm must be >= 1%s");
+    return OFMK_OK;
+}
+
+int check_detect_args(const void *in, int n, int H, int W, int L, const int32_t *counts, const uint8_t *bits) {
+    int rc = check_dims(n, H, W);
+    if (rc) return rc;
+    if (!in) return fail(OFMK_E_ARG, "null frame pointer%s");
+    if (L < 1) return fail(OFMK_E_ARG, "payload length L must be >= 1%s");
+    if (!counts && !bits) return fail(OFMK_E_ARG, "both outputs (counts, bits) are null%s");
+    return OFMK_OK;
+}
+
 Geom make_geom(int H, int W, const Workspace &ws, int frames = 0, int xcds = 0) {
     Geom g;
     g.frames = frames;
@@ -221,7 +268,8 @@ Geom make_geom(int H, int W, const Workspace &ws, int frames = 0, int xcds = 0) 
     return g;
 }
 
-dim3 block_grid(const Geom &g, int n) { return dim3((unsigned)((g.nblk + kThreads - 1) / kThreads), (unsigned)n); }
+// 2-D grid, tiles x frames (at most kMaxChunk): the kernels that gain nothing from the XCD order
+dim3 grid_2d(int units_per_frame, int n) { return dim3((unsigned)((units_per_frame + kThreads - 1) / kThreads), (unsigned)n); }
 
 // Linear grid of the frame kernels (common.hiph: xcd_tile): tiles x frames workgroups, padded to a multiple of the XCD count
 // the tile order assumes (xcds <= 1: linear order, no padding); the kernels take the frame count from their geometry argument.
@@ -242,11 +290,19 @@ void launch_copy_fringe(const uint8_t *in, uint8_t *out, int n, int H, int W, in
     const size_t fringe = (size_t)(H - Hc) * W * 3 + (size_t)Hc * (W - Wc) * 3;
     if (fringe == 0) return;
     const unsigned gx = (unsigned)((fringe + 256 * 4 - 1) / (256 * 4));
-    for (int f0 = 0; f0 < n; f0 += kMaxChunk) {
-        const int cf = n - f0 < kMaxChunk ? n - f0 : kMaxChunk;
+    for_chunks(n, kMaxChunk, [&](int f0, int cf) {
         const size_t fo = (size_t)f0 * H * W * 3;
         hipLaunchKernelGGL(copy_fringe_kernel, dim3(gx < 1024 ? gx : 1024, (unsigned)cf), dim3(256), 0, s, in + fo, out + fo, H, W, Hc, Wc);
-    }
+        return OFMK_OK;
+    });
+}
+
+// the same fringe into every copy of out ([copies][n][H][W][3])
+int launch_copy_fringe_copies(const uint8_t *in, uint8_t *out, int copies, int n, int H, int W, hipStream_t s) {
+    if (H % 8 == 0 && W % 8 == 0) return OFMK_OK;
+    for (int q = 0; q < copies; ++q) launch_copy_fringe(in, out + (size_t)q * n * H * W * 3, n, H, W, (H / 8) * 8, (W / 8) * 8, s);
+    HIP_TRY(hipGetLastError());
+    return OFMK_OK;
 }
 
 // zero_counts (optional): [n][L] position sums of these frames, cleared by the kernel for a finalize that follows
@@ -256,34 +312,43 @@ int launch_analyze(const void *frames, int src, int n, int H, int W, const Works
     // (no fill dispatch in front: the frame mean is summed from per-tile partial sums that every launch writes in full -- common.hiph: emit_block)
     const Geom g = make_geom(H, W, ws, n);
     const dim3 grid = xcd_grid(g.nblk, n);
-    const bool al = aligned_rows(frames, W, src == SRC_RGB8 ? 1 : 4);
     ScopedTiming timing(KIND_ANALYZE, cx);
-    if (src == SRC_RGB8) {
-        // Occupancy cap by an (unused) dynamic LDS reservation: 48 KiB per workgroup = 3 workgroups per CU instead of the
-        // 5 the registers allow.  Measured on the shipped kernel, interleaved in one session (profiles/r2_tuning_sweep.txt):
-        // 3 per CU 0.341 ms, 4 or 5 per CU 0.350, 2 per CU 0.367, 1 per CU 0.553 -- fewer resident wavefronts keep the
-        // window of frame bytes in flight smaller, which the memory system rewards (the bare read pattern shows the same).
-        constexpr unsigned kAnalyzeLdsCap = 48u * 1024u;
-        if (al) OFMK_TIMED_LAUNCH(timing, (analyze_kernel<SRC_RGB8, true>), grid, dim3(kThreads), kAnalyzeLdsCap, s, frames, g, ws.rec, ws.ysum, zero_counts, L);
-        else OFMK_TIMED_LAUNCH(timing, (analyze_kernel<SRC_RGB8, false>), grid, dim3(kThreads), kAnalyzeLdsCap, s, frames, g, ws.rec, ws.ysum, zero_counts, L);
-    } else {
-        if (al) OFMK_TIMED_LAUNCH(timing, (analyze_kernel<SRC_YUV32F, true>), grid, dim3(kThreads), 0, s, frames, g, ws.rec, ws.ysum, zero_counts, L);
-        else OFMK_TIMED_LAUNCH(timing, (analyze_kernel<SRC_YUV32F, false>), grid, dim3(kThreads), 0, s, frames, g, ws.rec, ws.ysum, zero_counts, L);
-    }
+    // Occupancy cap by an (unused) dynamic LDS reservation: 48 KiB per workgroup = 3 workgroups per CU instead of the
+    // 5 the registers allow.  Measured on the shipped kernel, interleaved in one session (profiles/r2_tuning_sweep.txt):
+    // 3 per CU 0.341 ms, 4 or 5 per CU 0.350, 2 per CU 0.367, 1 per CU 0.553 -- fewer resident wavefronts keep the
+    // window of frame bytes in flight smaller, which the memory system rewards (the bare read pattern shows the same).
+    constexpr unsigned kAnalyzeLdsCap = 48u * 1024u;
+    with_bool(aligned_rows(frames, W, src == SRC_RGB8 ? 1 : 4), [&](auto al) {
+        constexpr bool AL = decltype(al)::value;
+        if (src == SRC_RGB8) OFMK_TIMED_LAUNCH(timing, (analyze_kernel<SRC_RGB8, AL>), grid, dim3(kThreads), kAnalyzeLdsCap, s, frames, g, ws.rec, ws.ysum, zero_counts, L);
+        else OFMK_TIMED_LAUNCH(timing, (analyze_kernel<SRC_YUV32F, AL>), grid, dim3(kThreads), 0, s, frames, g, ws.rec, ws.ysum, zero_counts, L);
+    });
     HIP_TRY(hipGetLastError());
     return OFMK_OK;
 }
 
 int launch_finalize(FinArgs a, int n, const Ctx &cx) {
-    hipStream_t s = cx.s;
     const int per_wg = kThreads * kFinItems;
-    const unsigned gx = (unsigned)((a.N + per_wg - 1) / per_wg);
+    const dim3 grid((unsigned)((a.N + per_wg - 1) / per_wg), (unsigned)n);
     ScopedTiming timing(KIND_FINALIZE, cx);
-    const bool full = a.delta || a.soft || a.y_dc || a.lum || a.tex || a.step || a.c21_pre || a.c21_post;
-    if (full) OFMK_TIMED_LAUNCH(timing, finalize_kernel<true>, dim3(gx, (unsigned)n), dim3(kThreads), 0, s, a);
-    else OFMK_TIMED_LAUNCH(timing, finalize_kernel<false>, dim3(gx, (unsigned)n), dim3(kThreads), 0, s, a);
+    with_bool(a.delta || a.soft || a.y_dc || a.lum || a.tex || a.step || a.c21_pre || a.c21_post, [&](auto full) {
+        OFMK_TIMED_LAUNCH(timing, finalize_kernel<decltype(full)::value>, grid, dim3(kThreads), 0, cx.s, a);
+    });
     HIP_TRY(hipGetLastError());
     return OFMK_OK;
+}
+
+// What the DCT mark kernels (RGB, copies, planar) read besides the frames: the input frames' records in ws (launch_analyze).
+MarkArgs mark_args(const Workspace &ws, int H, int W, const uint8_t *wm, int n_wm, const int32_t *wm_row, double alpha) {
+    MarkArgs m;
+    m.rec = ws.rec;
+    m.ysum = ws.ysum;
+    m.wm = wm;
+    m.wm_row = wm_row;
+    m.n_wm = n_wm;
+    m.N = (int)((long long)H * W / 64);
+    m.alpha = alpha;
+    return m;
 }
 
 // Needs the input frames' records in ws.rec / ws.ysum (launch_analyze).  fused = true also leaves the
@@ -294,27 +359,16 @@ int launch_mark_rgb8(const uint8_t *in, uint8_t *out, int n, int H, int W, const
     const int xc = tile_xcds(cx, (size_t)n * H * W * 3);
     const Geom g = make_geom(H, W, ws, n, xc);
     const dim3 grid = xcd_grid(g.nblk, n, xc);
-    const bool al = aligned_rows(in, W, 1) && aligned_rows(out, W, 1);
-    MarkArgs m;
-    m.rec = ws.rec;
-    m.ysum = ws.ysum;
-    m.wm = wm;
-    m.wm_row = wm_row;
-    m.n_wm = n_wm;
-    m.N = (int)((long long)H * W / 64);
-    m.alpha = alpha;
+    const MarkArgs m = mark_args(ws, H, W, wm, n_wm, wm_row, alpha);
     {
         ScopedTiming timing(fused ? KIND_MARK_FUSED : KIND_MARK, cx);
-        if (fused) {
-            if (al) OFMK_TIMED_LAUNCH(timing, (mark_rgb8_kernel<true, true>), grid, dim3(kThreads), 0, s, in, out, g, m, ws.rec, ws.ysum2);
-            else OFMK_TIMED_LAUNCH(timing, (mark_rgb8_kernel<false, true>), grid, dim3(kThreads), 0, s, in, out, g, m, ws.rec, ws.ysum2);
-        } else if (xc > 1) {      // XCD-aware order: the marked rows are stored back to back at the end (dct_kernels.hiph: mark_rows HOLD; -2.5 %)
-            if (al) OFMK_TIMED_LAUNCH(timing, (mark_rgb8_kernel<true, false, true>), grid, dim3(kThreads), 0, s, in, out, g, m, ws.rec, ws.ysum2);
-            else OFMK_TIMED_LAUNCH(timing, (mark_rgb8_kernel<false, false, true>), grid, dim3(kThreads), 0, s, in, out, g, m, ws.rec, ws.ysum2);
-        } else {
-            if (al) OFMK_TIMED_LAUNCH(timing, (mark_rgb8_kernel<true, false>), grid, dim3(kThreads), 0, s, in, out, g, m, ws.rec, ws.ysum2);
-            else OFMK_TIMED_LAUNCH(timing, (mark_rgb8_kernel<false, false>), grid, dim3(kThreads), 0, s, in, out, g, m, ws.rec, ws.ysum2);
-        }
+        with_bool(aligned_rows(in, W, 1) && aligned_rows(out, W, 1), [&](auto al) {
+            constexpr bool AL = decltype(al)::value;
+            if (fused) OFMK_TIMED_LAUNCH(timing, (mark_rgb8_kernel<AL, true>), grid, dim3(kThreads), 0, s, in, out, g, m, ws.rec, ws.ysum2);
+            // XCD-aware order: the marked rows are stored back to back at the end (dct_kernels.hiph: mark_rows HOLD; -2.5 %)
+            else if (xc > 1) OFMK_TIMED_LAUNCH(timing, (mark_rgb8_kernel<AL, false, true>), grid, dim3(kThreads), 0, s, in, out, g, m, ws.rec, ws.ysum2);
+            else OFMK_TIMED_LAUNCH(timing, (mark_rgb8_kernel<AL, false>), grid, dim3(kThreads), 0, s, in, out, g, m, ws.rec, ws.ysum2);
+        });
     }
     HIP_TRY(hipGetLastError());
     if (in != out && (H % 8 || W % 8)) {
@@ -372,7 +426,7 @@ int embed_chunk(const void *in, void *out, int src, int f0, int cf, int H, int W
     a.delta = ws.delta;
     if ((rc = launch_finalize(a, cf, s))) return rc;
     const Geom g = make_geom(H, W, ws);
-    hipLaunchKernelGGL(mark_yuv32f_kernel, block_grid(g, cf), dim3(kThreads), 0, s.s, reinterpret_cast<float *>(pout), g, ws.delta);
+    hipLaunchKernelGGL(mark_yuv32f_kernel, grid_2d(g.nblk, cf), dim3(kThreads), 0, s.s, reinterpret_cast<float *>(pout), g, ws.delta);
     HIP_TRY(hipGetLastError());
     return OFMK_OK;
 }
@@ -393,122 +447,28 @@ int detect_chunk(const void *in, int src, int f0, int cf, int H, int W, int L, d
     return finalize_detect(f0, cf, H, W, L, alpha, counts, bits, ws, false, s);
 }
 
-// ---- DwtDctSvd codec ---------------------------------------------------------------------------
-int launch_svd_rgb8(const uint8_t *in, uint8_t *out, int n, int H, int W, int mode, SvdArgs a, const Ctx &cx) {
-    hipStream_t s = cx.s;
-    Workspace none;
-    none.plane = 0;
-    const Geom g = make_geom(H, W, none);
-    const bool al = aligned_rows(in, W, 1) && (mode == SVD_DETECT || aligned_rows(out, W, 1));
-    const size_t tiles = (size_t)(g.nblk + kThreads - 1) / kThreads;
-    // partial counts: every workgroup stores its own row, nothing to clear (OFMK_F_PARTIAL_COUNTS); else the frames' [L] sums are added into
-    if (a.counts && !a.partial) HIP_TRY(launch_zero(a.counts, (size_t)n * a.L * sizeof(int32_t), s));
-    if (a.bits && a.N > g.nblk) HIP_TRY(launch_zero(a.bits, (size_t)n * a.N, s));   // entries past (H/8)(W/8) stay 0
-    for (int f0 = 0; f0 < n; f0 += kMaxChunk) {
-        const int cf = n - f0 < kMaxChunk ? n - f0 : kMaxChunk;
-        const size_t fo = (size_t)f0 * g.frame_stride;
-        SvdArgs b = a;
-        if (b.wm_row) b.wm_row += f0;
-        if (b.counts) b.counts += (size_t)f0 * a.L * (a.partial ? tiles : 1);
-        if (b.bits) b.bits += (size_t)f0 * a.N;
-        Geom gc = g;
-        gc.frames = cf;
-        const dim3 grid = xcd_grid(g.nblk, cf);
-        ScopedTiming timing(KIND_SVD, cx);
-#define OFMK_SVD_LAUNCH(AL, MD, MU) OFMK_TIMED_LAUNCH(timing, (svd_rgb8_kernel<AL, MD, MU>), grid, dim3(kThreads), 0, s, in + fo, out ? out + fo : nullptr, gc, b)
-        const bool multi = a.scales[0] > 0.f || a.scales[2] > 0.f || !(a.scales[1] > 0.f);      // anything but the default [0, s, 0]
-        if (mode == SVD_DETECT) { if (al) OFMK_SVD_LAUNCH(true, SVD_DETECT, false); else OFMK_SVD_LAUNCH(false, SVD_DETECT, false); }
-        else if (mode == SVD_EMBED && !multi) { if (al) OFMK_SVD_LAUNCH(true, SVD_EMBED, false); else OFMK_SVD_LAUNCH(false, SVD_EMBED, false); }
-        else if (mode == SVD_EMBED) { if (al) OFMK_SVD_LAUNCH(true, SVD_EMBED, true); else OFMK_SVD_LAUNCH(false, SVD_EMBED, true); }
-        else if (!multi) { if (al) OFMK_SVD_LAUNCH(true, SVD_EMBED_VERIFY, false); else OFMK_SVD_LAUNCH(false, SVD_EMBED_VERIFY, false); }
-        else { if (al) OFMK_SVD_LAUNCH(true, SVD_EMBED_VERIFY, true); else OFMK_SVD_LAUNCH(false, SVD_EMBED_VERIFY, true); }
-#undef OFMK_SVD_LAUNCH
-    }
+// One chunk of frames [f0, f0+cf) after launch_analyze left their records in ws: every copy of them in one launch.
+int launch_mark_copies_rgb8(const uint8_t *in, uint8_t *out, int copies, int n, int f0, int cf, int H, int W, const uint8_t *wm,
+                            int n_wm, const int32_t *wm_rows, double alpha, const Workspace &ws, const Ctx &cx) {
+    const size_t fs = (size_t)H * W * 3;
+    const uint8_t *pin = in + (size_t)f0 * fs;
+    uint8_t *pout = out + (size_t)f0 * fs;
+    const int xc = tile_xcds(cx, (size_t)cf * fs);
+    const Geom g = make_geom(H, W, ws, cf, xc);
+    const dim3 grid = xcd_grid(g.nblk, cf, xc);
+    const MarkArgs m = mark_args(ws, H, W, wm, n_wm, nullptr, alpha);
+    CopyArgs k;
+    memset(&k, 0, sizeof(k));
+    k.copies = copies;
+    k.rows_stride = n;
+    k.wm_rows = wm_rows ? wm_rows + f0 : nullptr;
+    k.out_stride = (size_t)n * fs;
+    ScopedTiming timing(KIND_MARK, cx);
+    with_bool(aligned_rows(in, W, 1) && aligned_rows(out, W, 1), [&](auto al) {     // frame and copy strides are multiples of 8 when W is
+        OFMK_TIMED_LAUNCH(timing, mark_copies_rgb8_kernel<decltype(al)::value>, grid, dim3(kThreads), 0, cx.s, pin, pout, g, m, k);
+    });
     HIP_TRY(hipGetLastError());
-    if (mode != SVD_DETECT && in != out && (H % 8 || W % 8)) {
-        launch_copy_fringe(in, out, n, H, W, (H / 8) * 8, (W / 8) * 8, s);
-        HIP_TRY(hipGetLastError());
-    }
     return OFMK_OK;
-}
-
-// blk = 8: 16x16 pixel tiles (svd8_kernels.hiph).  a.N = H*W/64 (watermark row stride), a.N8 = H*W/256 (bits per frame).
-Geom8 make_geom8(int H, int W) {
-    Geom8 g;
-    g.W = W;
-    g.wt = ((W / 4) * 2) / 8;
-    g.inv_wt = g.wt ? 1.0f / (float)g.wt : 0.f;
-    g.ntile = (((H / 4) * 2) / 8) * g.wt;
-    g.frames = 0;
-    g.frame_stride = (size_t)H * W * 3;
-    return g;
-}
-
-int launch_svd8_rgb8(const uint8_t *in, uint8_t *out, int n, int H, int W, int mode, Svd8Args a, const Ctx &cx) {
-    hipStream_t s = cx.s;
-    const Geom8 g = make_geom8(H, W);
-    const size_t tiles = (size_t)(g.ntile + kThreads - 1) / kThreads;
-    if (a.counts && !a.partial) HIP_TRY(launch_zero(a.counts, (size_t)n * a.L * sizeof(int32_t), s));
-    if (a.bits && a.N8 > g.ntile) HIP_TRY(launch_zero(a.bits, (size_t)n * a.N8, s));    // entries past the tiles stay 0
-    const int Hc = (((H / 4) * 2) / 8) * 16, Wc = g.wt * 16;                                    // the region the tiles cover
-    if (g.ntile > 0) {
-        const bool al = W % 8 == 0 && (uintptr_t)in % 8 == 0 && (mode == SVD_DETECT || (uintptr_t)out % 8 == 0);
-        for (int f0 = 0; f0 < n; f0 += kMaxChunk) {
-            const int cf = n - f0 < kMaxChunk ? n - f0 : kMaxChunk;
-            const size_t fo = (size_t)f0 * g.frame_stride;
-            Svd8Args b = a;
-            if (b.wm_row) b.wm_row += f0;
-            if (b.counts) b.counts += (size_t)f0 * a.L * (a.partial ? tiles : 1);
-            if (b.bits) b.bits += (size_t)f0 * a.N8;
-            Geom8 gc = g;
-            gc.frames = cf;
-            const dim3 grid = xcd_grid(g.ntile, cf);
-            ScopedTiming timing(KIND_SVD, cx);
-#define OFMK_SVD8_LAUNCH(AL, MD, MU) OFMK_TIMED_LAUNCH(timing, (svd8_rgb8_kernel<AL, MD, MU>), grid, dim3(kThreads), 0, s, in + fo, out ? out + fo : nullptr, gc, b)
-            const bool multi = a.scales[0] > 0.f || a.scales[2] > 0.f || !(a.scales[1] > 0.f);      // anything but the default [0, s, 0]
-            if (mode == SVD_DETECT) { if (al) OFMK_SVD8_LAUNCH(true, SVD_DETECT, false); else OFMK_SVD8_LAUNCH(false, SVD_DETECT, false); }
-            else if (mode == SVD_EMBED && !multi) { if (al) OFMK_SVD8_LAUNCH(true, SVD_EMBED, false); else OFMK_SVD8_LAUNCH(false, SVD_EMBED, false); }
-            else if (mode == SVD_EMBED) { if (al) OFMK_SVD8_LAUNCH(true, SVD_EMBED, true); else OFMK_SVD8_LAUNCH(false, SVD_EMBED, true); }
-            else if (!multi) { if (al) OFMK_SVD8_LAUNCH(true, SVD_EMBED_VERIFY, false); else OFMK_SVD8_LAUNCH(false, SVD_EMBED_VERIFY, false); }
-            else { if (al) OFMK_SVD8_LAUNCH(true, SVD_EMBED_VERIFY, true); else OFMK_SVD8_LAUNCH(false, SVD_EMBED_VERIFY, true); }
-#undef OFMK_SVD8_LAUNCH
-        }
-        HIP_TRY(hipGetLastError());
-    }
-    if (mode != SVD_DETECT && in != out && (Hc != H || Wc != W)) {
-        launch_copy_fringe(in, out, n, H, W, Hc, Wc, s);
-        HIP_TRY(hipGetLastError());
-    }
-    return OFMK_OK;
-}
-
-// workgroups per frame of the DwtDctSvd frame kernels = rows of a frame's partial counts (OFMK_F_PARTIAL_COUNTS)
-int svd_count_tiles(int H, int W, int blk) {
-    const long long units = blk == 8 ? (long long)make_geom8(H, W).ntile : (long long)(H / 8) * (W / 8);
-    return (int)((units + kThreads - 1) / kThreads);
-}
-
-// OFMK_F_PARTIAL_COUNTS on a DwtDctSvd read-out: the workgroup's sums live in its LDS histogram, so L is bounded by it
-int check_partial(const ofmk_opts *o, int L, const int32_t *counts, int &partial) {
-    partial = (o && (o->flags & OFMK_F_PARTIAL_COUNTS)) ? 1 : 0;
-    if (partial && !counts) return fail(OFMK_E_ARG, "OFMK_F_PARTIAL_COUNTS without a counts buffer%s");
-    if (partial && L > kHistMax) return fail(OFMK_E_ARG, "OFMK_F_PARTIAL_COUNTS needs L <= 2048 (longer payloads: plain counts)%s");
-    return OFMK_OK;
-}
-
-int check_blk(int blk) {
-    if (blk != 4 && blk != 8)
-        return fail(OFMK_E_ARG, "blk must be 4 (the reference's default) or 8%s");
-    return OFMK_OK;
-}
-
-Svd8Args to_args8(const SvdArgs &a, int H, int W) {
-    Svd8Args b;
-    memset(&b, 0, sizeof(b));
-    b.wm = a.wm; b.wm_row = a.wm_row; b.n_wm = a.n_wm; b.counts = a.counts; b.bits = a.bits; b.partial = a.partial;
-    b.N = a.N; b.N8 = (int)((long long)H * W / 256); b.L = a.L;
-    for (int k = 0; k < 3; ++k) b.scales[k] = a.scales[k];
-    return b;
 }
 
 // ---- planar YUV 4:2:0 (I420 / NV12) -------------------------------------------------------------
@@ -536,10 +496,10 @@ PGeom make_pgeom(int layout, int H, int W, size_t plane) {
 int launch_analyze_yuv420(const uint8_t *frames, int layout, int n, int H, int W, const Workspace &ws, const Ctx &cx,
                           int32_t *zero_counts = nullptr, int L = 0) {
     const PGeom g = make_pgeom(layout, H, W, ws.plane);
-    const dim3 grid((unsigned)((g.nblk + kThreads - 1) / kThreads), (unsigned)n);     // 2-D grid: the planar kernels gain nothing from the XCD order
     ScopedTiming timing(KIND_PLANAR_ANALYZE, cx);
-    if (layout == OFMK_YUV_I420) OFMK_TIMED_LAUNCH(timing, analyze_yuv420_kernel<FMT_I420>, grid, dim3(kThreads), 0, cx.s, frames, g, ws.rec, ws.ysum, zero_counts, L);
-    else OFMK_TIMED_LAUNCH(timing, analyze_yuv420_kernel<FMT_NV12>, grid, dim3(kThreads), 0, cx.s, frames, g, ws.rec, ws.ysum, zero_counts, L);
+    with_fmt(layout, [&](auto fmt) {
+        OFMK_TIMED_LAUNCH(timing, analyze_yuv420_kernel<decltype(fmt)::value>, grid_2d(g.nblk, n), dim3(kThreads), 0, cx.s, frames, g, ws.rec, ws.ysum, zero_counts, L);
+    });
     HIP_TRY(hipGetLastError());
     return OFMK_OK;
 }
@@ -547,114 +507,91 @@ int launch_analyze_yuv420(const uint8_t *frames, int layout, int n, int H, int W
 int launch_mark_yuv420(const uint8_t *in, uint8_t *out, int layout, int n, int H, int W, const uint8_t *wm, int n_wm, const int32_t *wm_row,
                        double alpha, const Workspace &ws, bool fused, const Ctx &cx) {
     const PGeom g = make_pgeom(layout, H, W, ws.plane);
-    const dim3 grid((unsigned)((g.nblk + kThreads - 1) / kThreads), (unsigned)n);
-    MarkArgs m;
-    m.rec = ws.rec;
-    m.ysum = ws.ysum;
-    m.wm = wm;
-    m.wm_row = wm_row;
-    m.n_wm = n_wm;
-    m.N = (int)((long long)H * W / 64);
-    m.alpha = alpha;
+    const MarkArgs m = mark_args(ws, H, W, wm, n_wm, wm_row, alpha);
     ScopedTiming timing(KIND_PLANAR_MARK, cx);
-    if (layout == OFMK_YUV_I420) {
-        if (fused) OFMK_TIMED_LAUNCH(timing, (mark_yuv420_kernel<FMT_I420, true>), grid, dim3(kThreads), 0, cx.s, in, out, g, m, ws.rec, ws.ysum2);
-        else OFMK_TIMED_LAUNCH(timing, (mark_yuv420_kernel<FMT_I420, false>), grid, dim3(kThreads), 0, cx.s, in, out, g, m, ws.rec, ws.ysum2);
-    } else {
-        if (fused) OFMK_TIMED_LAUNCH(timing, (mark_yuv420_kernel<FMT_NV12, true>), grid, dim3(kThreads), 0, cx.s, in, out, g, m, ws.rec, ws.ysum2);
-        else OFMK_TIMED_LAUNCH(timing, (mark_yuv420_kernel<FMT_NV12, false>), grid, dim3(kThreads), 0, cx.s, in, out, g, m, ws.rec, ws.ysum2);
-    }
+    with_fmt(layout, [&](auto fmt) { with_bool(fused, [&](auto fu) {
+        OFMK_TIMED_LAUNCH(timing, (mark_yuv420_kernel<decltype(fmt)::value, decltype(fu)::value>), grid_2d(g.nblk, n), dim3(kThreads), 0, cx.s, in, out, g, m, ws.rec, ws.ysum2);
+    }); });
     HIP_TRY(hipGetLastError());
     return OFMK_OK;
 }
 
-// ---- DwtDctSvd codec on planar YUV 4:2:0 (svd_planar_kernels.hiph) --------------------------------------------------
-// The same grid as launch_svd_rgb8 / launch_svd8_rgb8 (one thread per tile, kThreads per workgroup, linear order), so partial
-// counts have ofmk_svd_count_tiles(H, W, blk) rows; the same zero-fills in front; timed under KIND_SVD.
-int launch_svd_yuv420(const uint8_t *in, uint8_t *out, int layout, int n, int H, int W, int mode, SvdArgs a, const Ctx &cx) {
-    hipStream_t s = cx.s;
+// embed_chunk / detect_chunk for planar frames: analyze + mark, and analyze + finalize, of frames [f0, f0+cf)
+int embed_chunk_yuv420(const uint8_t *in, uint8_t *out, int layout, int f0, int cf, int H, int W, const uint8_t *wm, int n_wm,
+                       const int32_t *wm_row, double alpha, const Workspace &ws, bool verify, const Ctx &cx,
+                       int32_t *zero_counts = nullptr, int L = 0) {
+    const size_t fo = (size_t)f0 * H * W * 3 / 2;
+    int rc = launch_analyze_yuv420(in + fo, layout, cf, H, W, ws, cx, zero_counts ? zero_counts + (size_t)f0 * L : nullptr, L);
+    if (rc) return rc;
+    return launch_mark_yuv420(in + fo, out + fo, layout, cf, H, W, wm, n_wm, wm_row ? wm_row + f0 : nullptr, alpha, ws, verify, cx);
+}
+
+int detect_chunk_yuv420(const uint8_t *in, int layout, int f0, int cf, int H, int W, int L, double alpha, int32_t *counts,
+                        uint8_t *bits, const Workspace &ws, const Ctx &cx) {
+    const size_t fo = (size_t)f0 * H * W * 3 / 2;
+    int rc = launch_analyze_yuv420(in + fo, layout, cf, H, W, ws, cx, counts ? counts + (size_t)f0 * L : nullptr, L);
+    if (rc) return rc;
+    return finalize_detect(f0, cf, H, W, L, alpha, counts, bits, ws, false, cx);
+}
+
+// yuv [n] planar 4:2:0 frames <-> rgb [n][H][W][3], in the direction to_rgb says
+int convert_yuv420(uint8_t *yuv, uint8_t *rgb, bool to_rgb, int layout, int n, int H, int W, void *stream, const ofmk_opts *opts) {
+    if (int orc = check_opts(opts)) return orc;
+    int rc = check_dims(n, H, W);
+    if (rc) return rc;
+    if (!yuv || !rgb) return fail(OFMK_E_ARG, "null pointer%s");
+    if ((rc = check_planar(layout, H, W, yuv, rgb))) return rc;
     const PGeom g = make_pgeom(layout, H, W, 0);
-    const size_t tiles = (size_t)(g.nblk + kThreads - 1) / kThreads;
-    if (a.counts && !a.partial) HIP_TRY(launch_zero(a.counts, (size_t)n * a.L * sizeof(int32_t), s));
-    const bool multi = a.scales[0] > 0.f || a.scales[2] > 0.f || !(a.scales[1] > 0.f);      // anything but the default [0, s, 0]
-    for (int f0 = 0; f0 < n; f0 += kMaxChunk) {
-        const int cf = n - f0 < kMaxChunk ? n - f0 : kMaxChunk;
-        const size_t fo = (size_t)f0 * g.frame_stride;
-        SvdArgs b = a;
-        if (b.wm_row) b.wm_row += f0;
-        if (b.counts) b.counts += (size_t)f0 * a.L * (a.partial ? tiles : 1);
-        if (b.bits) b.bits += (size_t)f0 * a.N;
-        const dim3 grid = xcd_grid(g.nblk, cf);
-        ScopedTiming timing(KIND_SVD, cx);
-#define OFMK_SVDP_LAUNCH(FMT, MD, MU) OFMK_TIMED_LAUNCH(timing, (svd_yuv420_kernel<FMT, MD, MU>), grid, dim3(kThreads), 0, s, in + fo, out ? out + fo : nullptr, g, cf, b)
-#define OFMK_SVDP_MODES(FMT)                                                                        \
-        if (mode == SVD_DETECT) OFMK_SVDP_LAUNCH(FMT, SVD_DETECT, false);                           \
-        else if (mode == SVD_EMBED && !multi) OFMK_SVDP_LAUNCH(FMT, SVD_EMBED, false);              \
-        else if (mode == SVD_EMBED) OFMK_SVDP_LAUNCH(FMT, SVD_EMBED, true);                         \
-        else if (!multi) OFMK_SVDP_LAUNCH(FMT, SVD_EMBED_VERIFY, false);                            \
-        else OFMK_SVDP_LAUNCH(FMT, SVD_EMBED_VERIFY, true)
-        if (layout == OFMK_YUV_I420) { OFMK_SVDP_MODES(FMT_I420); } else { OFMK_SVDP_MODES(FMT_NV12); }
-#undef OFMK_SVDP_MODES
-#undef OFMK_SVDP_LAUNCH
-    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    for_chunks(n, kMaxChunk, [&](int f0, int cf) {
+        uint8_t *py = yuv + (size_t)f0 * g.frame_stride, *pr = rgb + (size_t)f0 * H * W * 3;
+        with_fmt(layout, [&](auto fmt) {
+            if (to_rgb) hipLaunchKernelGGL(yuv420_to_rgb8_kernel<decltype(fmt)::value>, grid_2d(g.nblk, cf), dim3(kThreads), 0, s, py, pr, g);
+            else hipLaunchKernelGGL(rgb8_to_yuv420_kernel<decltype(fmt)::value>, grid_2d(g.nblk, cf), dim3(kThreads), 0, s, pr, py, g);
+        });
+        return OFMK_OK;
+    });
     HIP_TRY(hipGetLastError());
     return OFMK_OK;
 }
 
-// blk = 8.  The pixels outside the tiles' Hc x Wc region come out as the chain's: the 4:2:0 round trip of the input, written by
-// one more launch (also timed under KIND_SVD) -- also in place, where the RGB path has nothing to copy.
-int launch_svd8_yuv420(const uint8_t *in, uint8_t *out, int layout, int n, int H, int W, int mode, Svd8Args a, const Ctx &cx) {
-    hipStream_t s = cx.s;
-    const PGeom g = make_pgeom(layout, H, W, 0);
-    const Geom8 g8 = make_geom8(H, W);
-    const size_t tiles = (size_t)(g8.ntile + kThreads - 1) / kThreads;
-    if (a.counts && !a.partial) HIP_TRY(launch_zero(a.counts, (size_t)n * a.L * sizeof(int32_t), s));
-    if (a.bits && a.N8 > g8.ntile) HIP_TRY(launch_zero(a.bits, (size_t)n * a.N8, s));    // entries past the tiles stay 0
-    const bool multi = a.scales[0] > 0.f || a.scales[2] > 0.f || !(a.scales[1] > 0.f);
-    if (g8.ntile > 0) {
-        for (int f0 = 0; f0 < n; f0 += kMaxChunk) {
-            const int cf = n - f0 < kMaxChunk ? n - f0 : kMaxChunk;
-            const size_t fo = (size_t)f0 * g.frame_stride;
-            Svd8Args b = a;
-            if (b.wm_row) b.wm_row += f0;
-            if (b.counts) b.counts += (size_t)f0 * a.L * (a.partial ? tiles : 1);
-            if (b.bits) b.bits += (size_t)f0 * a.N8;
-            Geom8 gc = g8;
-            gc.frames = cf;
-            const dim3 grid = xcd_grid(g8.ntile, cf);
-            ScopedTiming timing(KIND_SVD, cx);
-#define OFMK_SVD8P_LAUNCH(FMT, MD, MU) OFMK_TIMED_LAUNCH(timing, (svd8_yuv420_kernel<FMT, MD, MU>), grid, dim3(kThreads), 0, s, in + fo, out ? out + fo : nullptr, g, gc, b)
-#define OFMK_SVD8P_MODES(FMT)                                                                       \
-            if (mode == SVD_DETECT) OFMK_SVD8P_LAUNCH(FMT, SVD_DETECT, false);                      \
-            else if (mode == SVD_EMBED && !multi) OFMK_SVD8P_LAUNCH(FMT, SVD_EMBED, false);         \
-            else if (mode == SVD_EMBED) OFMK_SVD8P_LAUNCH(FMT, SVD_EMBED, true);                    \
-            else if (!multi) OFMK_SVD8P_LAUNCH(FMT, SVD_EMBED_VERIFY, false);                       \
-            else OFMK_SVD8P_LAUNCH(FMT, SVD_EMBED_VERIFY, true)
-            if (layout == OFMK_YUV_I420) { OFMK_SVD8P_MODES(FMT_I420); } else { OFMK_SVD8P_MODES(FMT_NV12); }
-#undef OFMK_SVD8P_MODES
-#undef OFMK_SVD8P_LAUNCH
-        }
-        HIP_TRY(hipGetLastError());
-    }
-    const int hcb = (((H / 4) * 2) / 8) * 2, wcb = g8.wt * 2;                 // the tiles' Hc x Wc region in 8x8 pixel blocks
-    const int nfringe = g.nblk - hcb * wcb;
-    if (mode != SVD_DETECT && nfringe > 0) {
-        for (int f0 = 0; f0 < n; f0 += kMaxChunk) {
-            const int cf = n - f0 < kMaxChunk ? n - f0 : kMaxChunk;
-            const size_t fo = (size_t)f0 * g.frame_stride;
-            const dim3 grid((unsigned)((nfringe + kThreads - 1) / kThreads), (unsigned)cf);
-            ScopedTiming timing(KIND_SVD, cx);
-            if (layout == OFMK_YUV_I420) OFMK_TIMED_LAUNCH(timing, svd_fringe_yuv420_kernel<FMT_I420>, grid, dim3(kThreads), 0, s, in + fo, out + fo, g, hcb, wcb, nfringe);
-            else OFMK_TIMED_LAUNCH(timing, svd_fringe_yuv420_kernel<FMT_NV12>, grid, dim3(kThreads), 0, s, in + fo, out + fo, g, hcb, wcb, nfringe);
-        }
-        HIP_TRY(hipGetLastError());
-    }
+// ---- DwtDctSvd codec ---------------------------------------------------------------------------
+// blk = 8: 16x16 pixel tiles (svd8_kernels.hiph).  a.N = H*W/64 (watermark row stride), a.N8 = H*W/256 (bits per frame).
+Geom8 make_geom8(int H, int W) {
+    Geom8 g;
+    g.W = W;
+    g.wt = ((W / 4) * 2) / 8;
+    g.inv_wt = g.wt ? 1.0f / (float)g.wt : 0.f;
+    g.ntile = (((H / 4) * 2) / 8) * g.wt;
+    g.frames = 0;
+    g.frame_stride = (size_t)H * W * 3;
+    return g;
+}
+
+Geom svd_geom(int H, int W) {        // blk = 4: the DCT path's block geometry, no workspace behind it
+    Workspace none;
+    none.plane = 0;
+    return make_geom(H, W, none);
+}
+
+// workgroups per frame of the DwtDctSvd frame kernels = rows of a frame's partial counts (OFMK_F_PARTIAL_COUNTS)
+int svd_count_tiles(int H, int W, int blk) {
+    const long long units = blk == 8 ? (long long)make_geom8(H, W).ntile : (long long)(H / 8) * (W / 8);
+    return (int)((units + kThreads - 1) / kThreads);
+}
+
+// OFMK_F_PARTIAL_COUNTS on a DwtDctSvd read-out: the workgroup's sums live in its LDS histogram, so L is bounded by it
+int check_partial(const ofmk_opts *o, int L, const int32_t *counts, int &partial) {
+    partial = (o && (o->flags & OFMK_F_PARTIAL_COUNTS)) ? 1 : 0;
+    if (partial && !counts) return fail(OFMK_E_ARG, "OFMK_F_PARTIAL_COUNTS without a counts buffer%s");
+    if (partial && L > kHistMax) return fail(OFMK_E_ARG, "OFMK_F_PARTIAL_COUNTS needs L <= 2048 (longer payloads: plain counts)%s");
     return OFMK_OK;
 }
 
-int launch_svd_planar(const uint8_t *in, uint8_t *out, int layout, int n, int H, int W, int mode, const SvdArgs &a, int blk, const Ctx &cx) {
-    if (blk == 8) return launch_svd8_yuv420(in, out, layout, n, H, W, mode, to_args8(a, H, W), cx);
-    return launch_svd_yuv420(in, out, layout, n, H, W, mode, a, cx);
+int check_blk(int blk) {
+    if (blk != 4 && blk != 8)
+        return fail(OFMK_E_ARG, "blk must be 4 (the reference's default) or 8%s");
+    return OFMK_OK;
 }
 
 // scales: host double[3], one per YUV channel (dwt_dct_svd_encoder.py:6: scales=[0,15,0]); <= 0 leaves a channel alone
@@ -674,20 +611,155 @@ int set_scales(SvdArgs &a, const double *scales, bool need_channel1) {
     return OFMK_OK;
 }
 
-int check_embed_args(const void *in, const void *out, int n, int H, int W, const uint8_t *wm, int n_wm) {
-    int rc = check_dims(n, H, W);
-    if (rc) return rc;
-    if (!in || !out || !wm) return fail(OFMK_E_ARG, "null frame or watermark pointer%s");
-    if (n_wm < 1) return fail(OFMK_E_ARG, "n_wm must be >= 1%s");
+// The kernel arguments of one DwtDctSvd call: scales, watermark (embed) and outputs (read-out; L is 1 without one).
+// readout_opts: the call's opts where the call can read out -- OFMK_F_PARTIAL_COUNTS is then checked and taken; null for the
+// embed-only calls, which ignore that flag.  need_channel1: a read-out alone accepts scales without a positive entry.
+int make_svd_args(SvdArgs &a, int H, int W, const double *scales, bool need_channel1, const uint8_t *wm, int n_wm, const int32_t *wm_row,
+                  int L, int32_t *counts, uint8_t *bits, const ofmk_opts *readout_opts) {
+    memset(&a, 0, sizeof(a));
+    if (int rc = set_scales(a, scales, need_channel1)) return rc;
+    const bool readout = counts || bits;
+    if (readout && L < 1) return fail(OFMK_E_ARG, "payload length L must be >= 1%s");     // the copies call's outputs are optional
+    if (readout_opts)
+        if (int rc = check_partial(readout_opts, L, counts, a.partial)) return rc;
+    a.wm = wm;
+    a.wm_row = wm_row;
+    a.n_wm = n_wm;
+    a.counts = counts;
+    a.bits = bits;
+    a.N = (int)((long long)H * W / 64);
+    a.L = readout ? L : 1;
     return OFMK_OK;
 }
 
-int check_detect_args(const void *in, int n, int H, int W, int L, const int32_t *counts, const uint8_t *bits) {
-    int rc = check_dims(n, H, W);
+// The kernels for 16x16 tiles take the same arguments plus N8 = H*W/256, the bits per frame (svd8_kernels.hiph).
+Svd8Args to_args8(const SvdArgs &a, int N8) {
+    Svd8Args b;
+    memset(&b, 0, sizeof(b));
+    b.wm = a.wm; b.wm_row = a.wm_row; b.n_wm = a.n_wm; b.counts = a.counts; b.bits = a.bits; b.partial = a.partial;
+    b.N = a.N; b.N8 = N8; b.L = a.L;
+    for (int k = 0; k < 3; ++k) b.scales[k] = a.scales[k];
+    return b;
+}
+
+// scales[1] <= 0: the reference's decoder returns channel 1's (never written) bit array: all zeros
+int zero_svd_readout(int n, int H, int W, int blk, const SvdArgs &a, hipStream_t s) {
+    const size_t bits_per_frame = blk == 8 ? (size_t)((long long)H * W / 256) : (size_t)a.N;     // dwt_dct_svd_decoder.py:14
+    if (a.counts) HIP_TRY(launch_zero(a.counts, (size_t)n * a.L * sizeof(int32_t) * (a.partial ? (size_t)svd_count_tiles(H, W, blk) : 1), s));
+    if (a.bits) HIP_TRY(launch_zero(a.bits, (size_t)n * bits_per_frame, s));
+    return OFMK_OK;
+}
+
+// The launch path of every DwtDctSvd frame kernel (RGB and planar 4:2:0, blk 4 and 8, A/B copies).  A variant says how much
+// there is per frame; launch_svd clears the outputs, walks the frames in chunks of kMaxChunk and hands the variant one SvdChunk per
+// launch.  All variants use the linear grid (one thread per unit, kThreads per workgroup), so partial counts have
+// ofmk_svd_count_tiles(H, W, blk) rows.  The pixels the units do not cover are the variant's business after launch_svd returns.
+struct SvdPlan {
+    int units;              // threads per frame: (H/8)(W/8) blocks of 8x8 pixels (blk 4) or 16x16 tiles (blk 8)
+    int bits_per_frame;     // N = H*W/64 (blk 4) or N8 = H*W/256 (blk 8); entries past `units` stay 0
+    size_t frame_stride;    // bytes
+    int copies;             // outputs per input frame: counts / bits are [copies][n][...]
+};
+struct SvdChunk {
+    ScopedTiming timing;    // the KIND_SVD pair of this launch
+    dim3 grid;
+    size_t offset;          // bytes from the call's first frame to the chunk's
+    int f0, frames;
+    bool multi;             // a kernel that can mark channels 0 and 2 is needed
+    SvdArgs a;              // wm_row / counts / bits start at the chunk's first frame
+};
+
+template <class Launch>
+int launch_svd(const SvdPlan &p, int n, const SvdArgs &a, const Ctx &cx, Launch &&launch) {
+    const size_t count_rows = a.partial ? (size_t)(p.units + kThreads - 1) / kThreads : 1;
+    // partial counts: every workgroup stores its own row, nothing to clear (OFMK_F_PARTIAL_COUNTS); else the frames' [L] sums are added into
+    if (a.counts && !a.partial) HIP_TRY(launch_zero(a.counts, (size_t)p.copies * n * a.L * sizeof(int32_t), cx.s));
+    if (a.bits && p.bits_per_frame > p.units) HIP_TRY(launch_zero(a.bits, (size_t)p.copies * n * p.bits_per_frame, cx.s));
+    if (p.units == 0) return OFMK_OK;                // frames smaller than a 16x16 tile: no launch, no event pair
+    const bool multi = a.scales[0] > 0.f || a.scales[2] > 0.f || !(a.scales[1] > 0.f);      // anything but the default [0, s, 0]
+    for_chunks(n, kMaxChunk, [&](int f0, int cf) {
+        SvdChunk c{ScopedTiming(KIND_SVD, cx), xcd_grid(p.units, cf), (size_t)f0 * p.frame_stride, f0, cf, multi, a};
+        if (c.a.wm_row) c.a.wm_row += f0;
+        if (c.a.counts) c.a.counts += (size_t)f0 * a.L * count_rows;
+        if (c.a.bits) c.a.bits += (size_t)f0 * p.bits_per_frame;
+        launch(c);
+        return OFMK_OK;
+    });
+    HIP_TRY(hipGetLastError());
+    return OFMK_OK;
+}
+
+int launch_svd_rgb8(const uint8_t *in, uint8_t *out, int n, int H, int W, int mode, int blk, const SvdArgs &a, const Ctx &cx) {
+    int Hc = (H / 8) * 8, Wc = (W / 8) * 8;                // the region the units cover
+    int rc;
+    if (blk == 8) {
+        const Geom8 g = make_geom8(H, W);
+        const int N8 = (int)((long long)H * W / 256);
+        Hc = (((H / 4) * 2) / 8) * 16, Wc = g.wt * 16;
+        const bool al = W % 8 == 0 && (uintptr_t)in % 8 == 0 && (mode == SVD_DETECT || (uintptr_t)out % 8 == 0);
+        rc = launch_svd({g.ntile, N8, g.frame_stride, 1}, n, a, cx, [&](SvdChunk &c) {
+            Geom8 gc = g;
+            gc.frames = c.frames;
+            with_bool(al, [&](auto al_) { with_svd_mode(mode, c.multi, [&](auto md, auto mu) {
+                OFMK_TIMED_LAUNCH(c.timing, (svd8_rgb8_kernel<decltype(al_)::value, decltype(md)::value, decltype(mu)::value>), c.grid, dim3(kThreads), 0, cx.s,
+                                  in + c.offset, out ? out + c.offset : nullptr, gc, to_args8(c.a, N8));
+            }); });
+        });
+    } else {
+        const Geom g = svd_geom(H, W);
+        const bool al = aligned_rows(in, W, 1) && (mode == SVD_DETECT || aligned_rows(out, W, 1));
+        rc = launch_svd({g.nblk, a.N, g.frame_stride, 1}, n, a, cx, [&](SvdChunk &c) {
+            Geom gc = g;
+            gc.frames = c.frames;
+            with_bool(al, [&](auto al_) { with_svd_mode(mode, c.multi, [&](auto md, auto mu) {
+                OFMK_TIMED_LAUNCH(c.timing, (svd_rgb8_kernel<decltype(al_)::value, decltype(md)::value, decltype(mu)::value>), c.grid, dim3(kThreads), 0, cx.s,
+                                  in + c.offset, out ? out + c.offset : nullptr, gc, c.a);
+            }); });
+        });
+    }
     if (rc) return rc;
-    if (!in) return fail(OFMK_E_ARG, "null frame pointer%s");
-    if (L < 1) return fail(OFMK_E_ARG, "payload length L must be >= 1%s");
-    if (!counts && !bits) return fail(OFMK_E_ARG, "both outputs (counts, bits) are null%s");
+    if (mode != SVD_DETECT && in != out && (Hc != H || Wc != W)) {
+        launch_copy_fringe(in, out, n, H, W, Hc, Wc, cx.s);
+        HIP_TRY(hipGetLastError());
+    }
+    return OFMK_OK;
+}
+
+// Planar YUV 4:2:0 (svd_planar_kernels.hiph).  blk = 4: the 8x8 blocks cover the frame (H and W are multiples of 8).  blk = 8: the
+// pixels outside the tiles' Hc x Wc region come out as the chain's: the 4:2:0 round trip of the input, written by one more
+// launch (also timed under KIND_SVD) -- also in place, where the RGB path has nothing to copy.
+int launch_svd_yuv420(const uint8_t *in, uint8_t *out, int layout, int n, int H, int W, int mode, int blk, const SvdArgs &a, const Ctx &cx) {
+    const PGeom g = make_pgeom(layout, H, W, 0);
+    if (blk == 4)
+        return launch_svd({g.nblk, a.N, g.frame_stride, 1}, n, a, cx, [&](SvdChunk &c) {
+            with_fmt(layout, [&](auto fmt) { with_svd_mode(mode, c.multi, [&](auto md, auto mu) {
+                OFMK_TIMED_LAUNCH(c.timing, (svd_yuv420_kernel<decltype(fmt)::value, decltype(md)::value, decltype(mu)::value>), c.grid, dim3(kThreads), 0, cx.s,
+                                  in + c.offset, out ? out + c.offset : nullptr, g, c.frames, c.a);
+            }); });
+        });
+    const Geom8 g8 = make_geom8(H, W);
+    const int N8 = (int)((long long)H * W / 256);
+    int rc = launch_svd({g8.ntile, N8, g.frame_stride, 1}, n, a, cx, [&](SvdChunk &c) {
+        Geom8 gc = g8;
+        gc.frames = c.frames;
+        with_fmt(layout, [&](auto fmt) { with_svd_mode(mode, c.multi, [&](auto md, auto mu) {
+            OFMK_TIMED_LAUNCH(c.timing, (svd8_yuv420_kernel<decltype(fmt)::value, decltype(md)::value, decltype(mu)::value>), c.grid, dim3(kThreads), 0, cx.s,
+                              in + c.offset, out ? out + c.offset : nullptr, g, gc, to_args8(c.a, N8));
+        }); });
+    });
+    if (rc) return rc;
+    const int hcb = (((H / 4) * 2) / 8) * 2, wcb = g8.wt * 2;                 // the tiles' Hc x Wc region in 8x8 pixel blocks
+    const int nfringe = g.nblk - hcb * wcb;
+    if (mode == SVD_DETECT || nfringe <= 0) return OFMK_OK;
+    for_chunks(n, kMaxChunk, [&](int f0, int cf) {
+        const size_t fo = (size_t)f0 * g.frame_stride;
+        ScopedTiming timing(KIND_SVD, cx);
+        with_fmt(layout, [&](auto fmt) {
+            OFMK_TIMED_LAUNCH(timing, svd_fringe_yuv420_kernel<decltype(fmt)::value>, grid_2d(nfringe, cf), dim3(kThreads), 0, cx.s, in + fo, out + fo, g, hcb, wcb, nfringe);
+        });
+        return OFMK_OK;
+    });
+    HIP_TRY(hipGetLastError());
     return OFMK_OK;
 }
 
@@ -703,86 +775,32 @@ int check_copies(const void *in, const void *out, int copies, int n, int H, int 
     return OFMK_OK;
 }
 
-// One chunk of frames [f0, f0+cf) after launch_analyze left their records in ws: every copy of them in one launch.
-int launch_mark_copies_rgb8(const uint8_t *in, uint8_t *out, int copies, int n, int f0, int cf, int H, int W, const uint8_t *wm,
-                            int n_wm, const int32_t *wm_rows, double alpha, const Workspace &ws, const Ctx &cx) {
-    const size_t fs = (size_t)H * W * 3;
-    const uint8_t *pin = in + (size_t)f0 * fs;
-    uint8_t *pout = out + (size_t)f0 * fs;
-    const int xc = tile_xcds(cx, (size_t)cf * fs);
-    const Geom g = make_geom(H, W, ws, cf, xc);
-    const dim3 grid = xcd_grid(g.nblk, cf, xc);
-    const bool al = aligned_rows(in, W, 1) && aligned_rows(out, W, 1);     // frame and copy strides are multiples of 8 when W is
-    MarkArgs m;
-    m.rec = ws.rec;
-    m.ysum = ws.ysum;
-    m.wm = wm;
-    m.wm_row = nullptr;
-    m.n_wm = n_wm;
-    m.N = (int)((long long)H * W / 64);
-    m.alpha = alpha;
-    CopyArgs k;
-    memset(&k, 0, sizeof(k));
-    k.copies = copies;
-    k.rows_stride = n;
-    k.wm_rows = wm_rows ? wm_rows + f0 : nullptr;
-    k.out_stride = (size_t)n * fs;
-    ScopedTiming timing(KIND_MARK, cx);
-    if (al) OFMK_TIMED_LAUNCH(timing, mark_copies_rgb8_kernel<true>, grid, dim3(kThreads), 0, cx.s, pin, pout, g, m, k);
-    else OFMK_TIMED_LAUNCH(timing, mark_copies_rgb8_kernel<false>, grid, dim3(kThreads), 0, cx.s, pin, pout, g, m, k);
-    HIP_TRY(hipGetLastError());
-    return OFMK_OK;
-}
-
 // blk = 4: every copy from one launch per kMaxChunk frames; counts / bits of copy q at q * (the single-copy call's size).
-int launch_svd_copies_rgb8(const uint8_t *in, uint8_t *out, int copies, int n, int H, int W, const int32_t *wm_rows, SvdArgs a,
+// a.wm_row is null: the rows come from wm_rows ([copies][n], or null = copy q marks with row q).
+int launch_svd_copies_rgb8(const uint8_t *in, uint8_t *out, int copies, int n, int H, int W, const int32_t *wm_rows, const SvdArgs &a,
                            const Ctx &cx) {
-    hipStream_t s = cx.s;
-    Workspace none;
-    none.plane = 0;
-    const Geom g = make_geom(H, W, none);
+    const Geom g = svd_geom(H, W);
     const bool verify = a.counts || a.bits;
     const bool al = aligned_rows(in, W, 1) && aligned_rows(out, W, 1);
-    const size_t tiles = (size_t)(g.nblk + kThreads - 1) / kThreads;
     CopyArgs k;
     memset(&k, 0, sizeof(k));
     k.copies = copies;
     k.rows_stride = n;
     k.out_stride = (size_t)n * g.frame_stride;
-    k.counts_stride = (size_t)n * a.L * (a.partial ? tiles : 1);
+    k.counts_stride = (size_t)n * a.L * (a.partial ? (size_t)svd_count_tiles(H, W, 4) : 1);
     k.bits_stride = (size_t)n * a.N;
-    if (a.counts && !a.partial) HIP_TRY(launch_zero(a.counts, (size_t)copies * k.counts_stride * sizeof(int32_t), s));
-    if (a.bits && a.N > g.nblk) HIP_TRY(launch_zero(a.bits, (size_t)copies * k.bits_stride, s));   // entries past (H/8)(W/8) stay 0
-    const bool multi = a.scales[0] > 0.f || a.scales[2] > 0.f || !(a.scales[1] > 0.f);      // anything but the default [0, s, 0]
-    for (int f0 = 0; f0 < n; f0 += kMaxChunk) {
-        const int cf = n - f0 < kMaxChunk ? n - f0 : kMaxChunk;
-        const size_t fo = (size_t)f0 * g.frame_stride;
-        SvdArgs b = a;
-        b.wm_row = nullptr;
-        if (b.counts) b.counts += (size_t)f0 * a.L * (a.partial ? tiles : 1);
-        if (b.bits) b.bits += (size_t)f0 * a.N;
+    int rc = launch_svd({g.nblk, a.N, g.frame_stride, copies}, n, a, cx, [&](SvdChunk &c) {
         CopyArgs kc = k;
-        kc.wm_rows = wm_rows ? wm_rows + f0 : nullptr;
+        kc.wm_rows = wm_rows ? wm_rows + c.f0 : nullptr;
         Geom gc = g;
-        gc.frames = cf;
-        const dim3 grid = xcd_grid(g.nblk, cf);
-        ScopedTiming timing(KIND_SVD, cx);
-#define OFMK_SVDC_LAUNCH(AL, VF, MU) OFMK_TIMED_LAUNCH(timing, (svd_copies_rgb8_kernel<AL, VF, MU>), grid, dim3(kThreads), 0, s, in + fo, out + fo, gc, b, kc)
-#define OFMK_SVDC_MODES(AL)                                                                      \
-        if (!verify && !multi) OFMK_SVDC_LAUNCH(AL, false, false);                               \
-        else if (!verify) OFMK_SVDC_LAUNCH(AL, false, true);                                     \
-        else if (!multi) OFMK_SVDC_LAUNCH(AL, true, false);                                      \
-        else OFMK_SVDC_LAUNCH(AL, true, true)
-        if (al) { OFMK_SVDC_MODES(true); } else { OFMK_SVDC_MODES(false); }
-#undef OFMK_SVDC_MODES
-#undef OFMK_SVDC_LAUNCH
-    }
-    HIP_TRY(hipGetLastError());
-    if (H % 8 || W % 8) {
-        for (int q = 0; q < copies; ++q) launch_copy_fringe(in, out + (size_t)q * k.out_stride, n, H, W, (H / 8) * 8, (W / 8) * 8, s);
-        HIP_TRY(hipGetLastError());
-    }
-    return OFMK_OK;
+        gc.frames = c.frames;
+        with_bool(al, [&](auto al_) { with_bool(verify, [&](auto vf) { with_bool(c.multi, [&](auto mu) {
+            OFMK_TIMED_LAUNCH(c.timing, (svd_copies_rgb8_kernel<decltype(al_)::value, decltype(vf)::value, decltype(mu)::value>), c.grid, dim3(kThreads), 0, cx.s,
+                              in + c.offset, out + c.offset, gc, c.a, kc);
+        }); }); });
+    });
+    if (rc) return rc;
+    return launch_copy_fringe_copies(in, out, copies, n, H, W, cx.s);
 }
 
 }  // namespace
@@ -806,11 +824,7 @@ int ofmk_embed_rgb8(const uint8_t *in, uint8_t *out, int n, int H, int W, const 
     Workspace ws;
     if ((rc = carve(workspace, workspace_bytes, H, W, chunk_frames, ws))) return rc;
     const Ctx cx = make_ctx(stream, opts);
-    for (int f0 = 0; f0 < n; f0 += ws.frames) {
-        const int cf = n - f0 < ws.frames ? n - f0 : ws.frames;
-        if ((rc = embed_chunk(in, out, SRC_RGB8, f0, cf, H, W, wm, n_wm, wm_row, alpha, ws, false, cx))) return rc;
-    }
-    return OFMK_OK;
+    return for_chunks(n, ws.frames, [&](int f0, int cf) { return embed_chunk(in, out, SRC_RGB8, f0, cf, H, W, wm, n_wm, wm_row, alpha, ws, false, cx); });
 }
 
 int ofmk_detect_rgb8(const uint8_t *in, int n, int H, int W, int L, double alpha, int32_t *counts, uint8_t *bits,
@@ -821,11 +835,8 @@ int ofmk_detect_rgb8(const uint8_t *in, int n, int H, int W, int L, double alpha
     Workspace ws;
     if ((rc = carve(workspace, workspace_bytes, H, W, chunk_frames, ws))) return rc;
     const Ctx cx = make_ctx(stream, opts);
-    for (int f0 = 0; f0 < n; f0 += ws.frames) {      // counts are cleared by each chunk's analyze kernel
-        const int cf = n - f0 < ws.frames ? n - f0 : ws.frames;
-        if ((rc = detect_chunk(in, SRC_RGB8, f0, cf, H, W, L, alpha, counts, bits, ws, cx))) return rc;
-    }
-    return OFMK_OK;
+    // counts are cleared by each chunk's analyze kernel
+    return for_chunks(n, ws.frames, [&](int f0, int cf) { return detect_chunk(in, SRC_RGB8, f0, cf, H, W, L, alpha, counts, bits, ws, cx); });
 }
 
 // Build extension, not reference semantics: per payload position the sum over the frame's blocks
@@ -843,15 +854,13 @@ int ofmk_detect_soft_rgb8(const uint8_t *in, int n, int H, int W, int L, double 
     const Ctx cx = make_ctx(stream, opts);
     HIP_TRY(launch_zero(soft, (size_t)n * L * sizeof(long long), cx.s));
     const size_t fs = (size_t)H * W * 3;
-    for (int f0 = 0; f0 < n; f0 += ws.frames) {
-        const int cf = n - f0 < ws.frames ? n - f0 : ws.frames;
-        if ((rc = launch_analyze(in + (size_t)f0 * fs, SRC_RGB8, cf, H, W, ws, cx))) return rc;
+    return for_chunks(n, ws.frames, [&](int f0, int cf) {
+        if (int rc = launch_analyze(in + (size_t)f0 * fs, SRC_RGB8, cf, H, W, ws, cx)) return rc;
         FinArgs a = fin_base(ws, H, W, alpha);
         a.L = L;
         a.soft = soft + (size_t)f0 * L;
-        if ((rc = launch_finalize(a, cf, cx))) return rc;
-    }
-    return OFMK_OK;
+        return launch_finalize(a, cf, cx);
+    });
 }
 
 int ofmk_embed_detect_rgb8(const uint8_t *in, uint8_t *out, int n, int H, int W, const uint8_t *wm, int n_wm,
@@ -865,17 +874,14 @@ int ofmk_embed_detect_rgb8(const uint8_t *in, uint8_t *out, int n, int H, int W,
     Workspace ws;
     if ((rc = carve(workspace, workspace_bytes, H, W, chunk_frames, ws))) return rc;
     const Ctx cx = make_ctx(stream, opts);
-    for (int f0 = 0; f0 < n; f0 += ws.frames) {
-        const int cf = n - f0 < ws.frames ? n - f0 : ws.frames;
+    return for_chunks(n, ws.frames, [&](int f0, int cf) {
         if (!(cx.flags & OFMK_F_SEPARATE_DETECT)) {
-            if ((rc = embed_chunk(in, out, SRC_RGB8, f0, cf, H, W, wm, n_wm, wm_row, alpha, ws, true, cx, counts, L))) return rc;
-            if ((rc = finalize_detect(f0, cf, H, W, L, alpha, counts, bits, ws, true, cx))) return rc;
-        } else {
-            if ((rc = embed_chunk(in, out, SRC_RGB8, f0, cf, H, W, wm, n_wm, wm_row, alpha, ws, false, cx))) return rc;
-            if ((rc = detect_chunk(out, SRC_RGB8, f0, cf, H, W, L, alpha, counts, bits, ws, cx))) return rc;
+            if (int rc = embed_chunk(in, out, SRC_RGB8, f0, cf, H, W, wm, n_wm, wm_row, alpha, ws, true, cx, counts, L)) return rc;
+            return finalize_detect(f0, cf, H, W, L, alpha, counts, bits, ws, true, cx);
         }
-    }
-    return OFMK_OK;
+        if (int rc = embed_chunk(in, out, SRC_RGB8, f0, cf, H, W, wm, n_wm, wm_row, alpha, ws, false, cx)) return rc;
+        return detect_chunk(out, SRC_RGB8, f0, cf, H, W, L, alpha, counts, bits, ws, cx);
+    });
 }
 
 int ofmk_encode_yuv32f(float *yuv, int n, int H, int W, const uint8_t *wm, int n_wm, const int32_t *wm_row,
@@ -887,11 +893,7 @@ int ofmk_encode_yuv32f(float *yuv, int n, int H, int W, const uint8_t *wm, int n
     Workspace ws;
     if ((rc = carve(workspace, workspace_bytes, H, W, chunk_frames, ws))) return rc;
     const Ctx cx = make_ctx(stream, opts);
-    for (int f0 = 0; f0 < n; f0 += ws.frames) {
-        const int cf = n - f0 < ws.frames ? n - f0 : ws.frames;
-        if ((rc = embed_chunk(yuv, yuv, SRC_YUV32F, f0, cf, H, W, wm, n_wm, wm_row, alpha, ws, false, cx))) return rc;
-    }
-    return OFMK_OK;
+    return for_chunks(n, ws.frames, [&](int f0, int cf) { return embed_chunk(yuv, yuv, SRC_YUV32F, f0, cf, H, W, wm, n_wm, wm_row, alpha, ws, false, cx); });
 }
 
 int ofmk_decode_yuv32f(const float *yuv, int n, int H, int W, int L, double alpha, int32_t *counts, uint8_t *bits,
@@ -902,11 +904,7 @@ int ofmk_decode_yuv32f(const float *yuv, int n, int H, int W, int L, double alph
     Workspace ws;
     if ((rc = carve(workspace, workspace_bytes, H, W, chunk_frames, ws))) return rc;
     const Ctx cx = make_ctx(stream, opts);
-    for (int f0 = 0; f0 < n; f0 += ws.frames) {
-        const int cf = n - f0 < ws.frames ? n - f0 : ws.frames;
-        if ((rc = detect_chunk(yuv, SRC_YUV32F, f0, cf, H, W, L, alpha, counts, bits, ws, cx))) return rc;
-    }
-    return OFMK_OK;
+    return for_chunks(n, ws.frames, [&](int f0, int cf) { return detect_chunk(yuv, SRC_YUV32F, f0, cf, H, W, L, alpha, counts, bits, ws, cx); });
 }
 
 int ofmk_debug_planes(const void *frame, int src_is_yuv32f, int H, int W, double alpha, const uint8_t *wm,
@@ -962,14 +960,11 @@ int ofmk_svd_embed_rgb8(const uint8_t *in, uint8_t *out, int n, int H, int W, co
     if (rc) return rc;
     if ((rc = check_blk(blk))) return rc;
     SvdArgs a;
-    memset(&a, 0, sizeof(a));
-    if ((rc = set_scales(a, scales, false))) return rc;
-    a.wm = wm; a.wm_row = wm_row; a.n_wm = n_wm; a.N = (int)((long long)H * W / 64); a.L = 1;
-    if (blk == 8) return launch_svd8_rgb8(in, out, n, H, W, SVD_EMBED, to_args8(a, H, W), make_ctx(stream, opts));
-    return launch_svd_rgb8(in, out, n, H, W, SVD_EMBED, a, make_ctx(stream, opts));
+    if ((rc = make_svd_args(a, H, W, scales, false, wm, n_wm, wm_row, 1, nullptr, nullptr, nullptr))) return rc;
+    return launch_svd_rgb8(in, out, n, H, W, SVD_EMBED, blk, a, make_ctx(stream, opts));
 }
 
-// scales[1] <= 0: the reference's decoder returns channel 1's (never written) bit array: all zeros
+// scales[1] <= 0: zeroed counts / bits (zero_svd_readout)
 int ofmk_svd_detect_rgb8(const uint8_t *in, int n, int H, int W, int L, const double *scales, int blk, int32_t *counts, uint8_t *bits,
                          void *stream, const ofmk_opts *opts) {
     if (int orc = check_opts(opts)) return orc;
@@ -977,19 +972,9 @@ int ofmk_svd_detect_rgb8(const uint8_t *in, int n, int H, int W, int L, const do
     if (rc) return rc;
     if ((rc = check_blk(blk))) return rc;
     SvdArgs a;
-    memset(&a, 0, sizeof(a));
-    if ((rc = set_scales(a, scales, true))) return rc;
-    if ((rc = check_partial(opts, L, counts, a.partial))) return rc;
-    a.counts = counts; a.bits = bits; a.N = (int)((long long)H * W / 64); a.L = L;
-    const size_t bits_per_frame = blk == 8 ? (size_t)((long long)H * W / 256) : (size_t)a.N;     // dwt_dct_svd_decoder.py:14
-    if (!(a.scales[1] > 0.f)) {
-        hipStream_t s = static_cast<hipStream_t>(stream);
-        if (counts) HIP_TRY(launch_zero(counts, (size_t)n * L * sizeof(int32_t) * (a.partial ? (size_t)svd_count_tiles(H, W, blk) : 1), s));
-        if (bits) HIP_TRY(launch_zero(bits, (size_t)n * bits_per_frame, s));
-        return OFMK_OK;
-    }
-    if (blk == 8) return launch_svd8_rgb8(in, nullptr, n, H, W, SVD_DETECT, to_args8(a, H, W), make_ctx(stream, opts));
-    return launch_svd_rgb8(in, nullptr, n, H, W, SVD_DETECT, a, make_ctx(stream, opts));
+    if ((rc = make_svd_args(a, H, W, scales, true, nullptr, 0, nullptr, L, counts, bits, opts))) return rc;
+    if (!(a.scales[1] > 0.f)) return zero_svd_readout(n, H, W, blk, a, static_cast<hipStream_t>(stream));
+    return launch_svd_rgb8(in, nullptr, n, H, W, SVD_DETECT, blk, a, make_ctx(stream, opts));
 }
 
 int ofmk_svd_embed_detect_rgb8(const uint8_t *in, uint8_t *out, int n, int H, int W, const uint8_t *wm, int n_wm,
@@ -1001,13 +986,8 @@ int ofmk_svd_embed_detect_rgb8(const uint8_t *in, uint8_t *out, int n, int H, in
     if ((rc = check_blk(blk))) return rc;
     if ((rc = check_detect_args(out, n, H, W, L, counts, bits))) return rc;
     SvdArgs a;
-    memset(&a, 0, sizeof(a));
-    if ((rc = set_scales(a, scales, false))) return rc;
-    if ((rc = check_partial(opts, L, counts, a.partial))) return rc;
-    a.wm = wm; a.wm_row = wm_row; a.n_wm = n_wm; a.counts = counts; a.bits = bits;
-    a.N = (int)((long long)H * W / 64); a.L = L;
-    if (blk == 8) return launch_svd8_rgb8(in, out, n, H, W, SVD_EMBED_VERIFY, to_args8(a, H, W), make_ctx(stream, opts));
-    return launch_svd_rgb8(in, out, n, H, W, SVD_EMBED_VERIFY, a, make_ctx(stream, opts));
+    if ((rc = make_svd_args(a, H, W, scales, false, wm, n_wm, wm_row, L, counts, bits, opts))) return rc;
+    return launch_svd_rgb8(in, out, n, H, W, SVD_EMBED_VERIFY, blk, a, make_ctx(stream, opts));
 }
 
 int ofmk_embed_copies_rgb8(const uint8_t *in, uint8_t *out, int copies, int n, int H, int W, const uint8_t *wm, int n_wm,
@@ -1020,17 +1000,12 @@ int ofmk_embed_copies_rgb8(const uint8_t *in, uint8_t *out, int copies, int n, i
     Workspace ws;
     if ((rc = carve(workspace, workspace_bytes, H, W, chunk_frames, ws))) return rc;
     const Ctx cx = make_ctx(stream, opts);
-    const size_t fs = (size_t)H * W * 3;
-    for (int f0 = 0; f0 < n; f0 += ws.frames) {      // one analysis per chunk serves every copy
-        const int cf = n - f0 < ws.frames ? n - f0 : ws.frames;
-        if ((rc = launch_analyze(in + (size_t)f0 * fs, SRC_RGB8, cf, H, W, ws, cx))) return rc;
-        if ((rc = launch_mark_copies_rgb8(in, out, copies, n, f0, cf, H, W, wm, n_wm, wm_rows, alpha, ws, cx))) return rc;
-    }
-    if (H % 8 || W % 8) {
-        for (int q = 0; q < copies; ++q) launch_copy_fringe(in, out + (size_t)q * n * fs, n, H, W, (H / 8) * 8, (W / 8) * 8, cx.s);
-        HIP_TRY(hipGetLastError());
-    }
-    return OFMK_OK;
+    rc = for_chunks(n, ws.frames, [&](int f0, int cf) {      // one analysis per chunk serves every copy
+        if (int rc = launch_analyze(in + (size_t)f0 * H * W * 3, SRC_RGB8, cf, H, W, ws, cx)) return rc;
+        return launch_mark_copies_rgb8(in, out, copies, n, f0, cf, H, W, wm, n_wm, wm_rows, alpha, ws, cx);
+    });
+    if (rc) return rc;
+    return launch_copy_fringe_copies(in, out, copies, n, H, W, cx.s);
 }
 
 int ofmk_svd_embed_copies_rgb8(const uint8_t *in, uint8_t *out, int copies, int n, int H, int W, const uint8_t *wm, int n_wm,
@@ -1042,13 +1017,8 @@ int ofmk_svd_embed_copies_rgb8(const uint8_t *in, uint8_t *out, int copies, int 
     if ((rc = check_copies(in, out, copies, n, H, W))) return rc;
     if ((rc = check_blk(blk))) return rc;
     SvdArgs a;
-    memset(&a, 0, sizeof(a));
-    if ((rc = set_scales(a, scales, false))) return rc;
-    const bool verify = counts || bits;
-    if (verify && L < 1) return fail(OFMK_E_ARG, "payload length L must be >= 1%s");
-    if ((rc = check_partial(opts, L, counts, a.partial))) return rc;
-    a.wm = wm; a.n_wm = n_wm; a.counts = counts; a.bits = bits;
-    a.N = (int)((long long)H * W / 64); a.L = verify ? L : 1;
+    if ((rc = make_svd_args(a, H, W, scales, false, wm, n_wm, nullptr, L, counts, bits, opts))) return rc;
+    const int mode = counts || bits ? SVD_EMBED_VERIFY : SVD_EMBED;
     const Ctx cx = make_ctx(stream, opts);
     if (blk == 4) return launch_svd_copies_rgb8(in, out, copies, n, H, W, wm_rows, a, cx);
     // blk = 8: the single-copy launches once per copy (no fused copies kernel for 16x16 tiles)
@@ -1065,8 +1035,7 @@ int ofmk_svd_embed_copies_rgb8(const uint8_t *in, uint8_t *out, int copies, int 
         }
         if (b.counts) b.counts += (size_t)q * n * a.L * count_rows;
         if (b.bits) b.bits += (size_t)q * n * bits8;
-        if ((rc = launch_svd8_rgb8(in, out + (size_t)q * n * fs, n, H, W, verify ? SVD_EMBED_VERIFY : SVD_EMBED, to_args8(b, H, W), cx)))
-            return rc;
+        if ((rc = launch_svd_rgb8(in, out + (size_t)q * n * fs, n, H, W, mode, 8, b, cx))) return rc;
     }
     return OFMK_OK;
 }
@@ -1079,25 +1048,21 @@ int ofmk_svd_encode_yuv32f(float *yuv, int n, int H, int W, const uint8_t *wm, i
     if ((rc = check_blk(blk))) return rc;
     if (n > kMaxChunk) return fail(OFMK_E_ARG, "too many frames%s");
     SvdArgs a;
-    memset(&a, 0, sizeof(a));
-    if ((rc = set_scales(a, scales, false))) return rc;
-    a.wm = wm; a.wm_row = wm_row; a.n_wm = n_wm; a.N = (int)((long long)H * W / 64); a.L = 1;
+    if ((rc = make_svd_args(a, H, W, scales, false, wm, n_wm, wm_row, 1, nullptr, nullptr, nullptr))) return rc;
     const Ctx cx = make_ctx(stream, opts);
     if (blk == 8) {
         const Geom8 g8 = make_geom8(H, W);
         if (g8.ntile > 0) {                               // an event pair is reserved only for a launch that happens
             ScopedTiming timing(KIND_SVD, cx);
-            OFMK_TIMED_LAUNCH(timing, (svd8_yuv32f_kernel<SVD_EMBED>), dim3((unsigned)((g8.ntile + kThreads - 1) / kThreads), (unsigned)n), dim3(kThreads), 0,
-                              cx.s, yuv, g8, to_args8(a, H, W));
+            OFMK_TIMED_LAUNCH(timing, (svd8_yuv32f_kernel<SVD_EMBED>), grid_2d(g8.ntile, n), dim3(kThreads), 0, cx.s, yuv, g8,
+                              to_args8(a, (int)((long long)H * W / 256)));
         }
         HIP_TRY(hipGetLastError());
         return OFMK_OK;
     }
-    Workspace none;
-    none.plane = 0;
-    const Geom g = make_geom(H, W, none);
+    const Geom g = svd_geom(H, W);
     ScopedTiming timing(KIND_SVD, cx);                    // the plugin path's launches are timed like every other
-    OFMK_TIMED_LAUNCH(timing, (svd_yuv32f_kernel<SVD_EMBED>), block_grid(g, n), dim3(kThreads), 0, cx.s, yuv, g, a);
+    OFMK_TIMED_LAUNCH(timing, (svd_yuv32f_kernel<SVD_EMBED>), grid_2d(g.nblk, n), dim3(kThreads), 0, cx.s, yuv, g, a);
     HIP_TRY(hipGetLastError());
     return OFMK_OK;
 }
@@ -1111,29 +1076,24 @@ int ofmk_svd_decode_yuv32f(const float *yuv, int n, int H, int W, const double *
     if (!yuv || !bits) return fail(OFMK_E_ARG, "null pointer%s");
     if (n > kMaxChunk) return fail(OFMK_E_ARG, "too many frames%s");
     SvdArgs a;
-    memset(&a, 0, sizeof(a));
-    if ((rc = set_scales(a, scales, true))) return rc;
-    a.bits = bits; a.N = (int)((long long)H * W / 64); a.L = 1;
+    if ((rc = make_svd_args(a, H, W, scales, true, nullptr, 0, nullptr, 1, nullptr, bits, nullptr))) return rc;
     const Ctx cx = make_ctx(stream, opts);
     hipStream_t s = cx.s;
     if (blk == 8) {                                       // bits: [n][H*W/256] (dwt_dct_svd_decoder.py:14)
         const Geom8 g8 = make_geom8(H, W);
-        const Svd8Args a8 = to_args8(a, H, W);
+        const Svd8Args a8 = to_args8(a, (int)((long long)H * W / 256));
         if (a8.N8 > g8.ntile || !(a.scales[1] > 0.f)) HIP_TRY(launch_zero(bits, (size_t)n * a8.N8, s));
         if (!(a.scales[1] > 0.f) || g8.ntile == 0) return OFMK_OK;
         ScopedTiming timing(KIND_SVD, cx);
-        OFMK_TIMED_LAUNCH(timing, (svd8_yuv32f_kernel<SVD_DETECT>), dim3((unsigned)((g8.ntile + kThreads - 1) / kThreads), (unsigned)n), dim3(kThreads), 0, s,
-                          const_cast<float *>(yuv), g8, a8);
+        OFMK_TIMED_LAUNCH(timing, (svd8_yuv32f_kernel<SVD_DETECT>), grid_2d(g8.ntile, n), dim3(kThreads), 0, s, const_cast<float *>(yuv), g8, a8);
         HIP_TRY(hipGetLastError());
         return OFMK_OK;
     }
-    Workspace none;
-    none.plane = 0;
-    const Geom g = make_geom(H, W, none);
+    const Geom g = svd_geom(H, W);
     if (a.N > g.nblk || !(a.scales[1] > 0.f)) HIP_TRY(launch_zero(bits, (size_t)n * a.N, s));
     if (!(a.scales[1] > 0.f)) return OFMK_OK;
     ScopedTiming timing(KIND_SVD, cx);
-    OFMK_TIMED_LAUNCH(timing, (svd_yuv32f_kernel<SVD_DETECT>), block_grid(g, n), dim3(kThreads), 0, s, const_cast<float *>(yuv), g, a);
+    OFMK_TIMED_LAUNCH(timing, (svd_yuv32f_kernel<SVD_DETECT>), grid_2d(g.nblk, n), dim3(kThreads), 0, s, const_cast<float *>(yuv), g, a);
     HIP_TRY(hipGetLastError());
     return OFMK_OK;
 }
@@ -1175,14 +1135,7 @@ int ofmk_embed_yuv420(const uint8_t *in, uint8_t *out, int layout, int n, int H,
     Workspace ws;
     if ((rc = carve(workspace, workspace_bytes, H, W, chunk_frames, ws))) return rc;
     const Ctx cx = make_ctx(stream, opts);
-    const size_t fs = (size_t)H * W * 3 / 2;
-    for (int f0 = 0; f0 < n; f0 += ws.frames) {
-        const int cf = n - f0 < ws.frames ? n - f0 : ws.frames;
-        if ((rc = launch_analyze_yuv420(in + (size_t)f0 * fs, layout, cf, H, W, ws, cx))) return rc;
-        if ((rc = launch_mark_yuv420(in + (size_t)f0 * fs, out + (size_t)f0 * fs, layout, cf, H, W, wm, n_wm, wm_row ? wm_row + f0 : nullptr,
-                                     alpha, ws, false, cx))) return rc;
-    }
-    return OFMK_OK;
+    return for_chunks(n, ws.frames, [&](int f0, int cf) { return embed_chunk_yuv420(in, out, layout, f0, cf, H, W, wm, n_wm, wm_row, alpha, ws, false, cx); });
 }
 
 int ofmk_detect_yuv420(const uint8_t *in, int layout, int n, int H, int W, int L, double alpha, int32_t *counts, uint8_t *bits,
@@ -1194,13 +1147,7 @@ int ofmk_detect_yuv420(const uint8_t *in, int layout, int n, int H, int W, int L
     Workspace ws;
     if ((rc = carve(workspace, workspace_bytes, H, W, chunk_frames, ws))) return rc;
     const Ctx cx = make_ctx(stream, opts);
-    const size_t fs = (size_t)H * W * 3 / 2;
-    for (int f0 = 0; f0 < n; f0 += ws.frames) {
-        const int cf = n - f0 < ws.frames ? n - f0 : ws.frames;
-        if ((rc = launch_analyze_yuv420(in + (size_t)f0 * fs, layout, cf, H, W, ws, cx, counts ? counts + (size_t)f0 * L : nullptr, L))) return rc;
-        if ((rc = finalize_detect(f0, cf, H, W, L, alpha, counts, bits, ws, false, cx))) return rc;
-    }
-    return OFMK_OK;
+    return for_chunks(n, ws.frames, [&](int f0, int cf) { return detect_chunk_yuv420(in, layout, f0, cf, H, W, L, alpha, counts, bits, ws, cx); });
 }
 
 int ofmk_embed_detect_yuv420(const uint8_t *in, uint8_t *out, int layout, int n, int H, int W, const uint8_t *wm, int n_wm,
@@ -1214,23 +1161,14 @@ int ofmk_embed_detect_yuv420(const uint8_t *in, uint8_t *out, int layout, int n,
     Workspace ws;
     if ((rc = carve(workspace, workspace_bytes, H, W, chunk_frames, ws))) return rc;
     const Ctx cx = make_ctx(stream, opts);
-    const size_t fs = (size_t)H * W * 3 / 2;
-    const bool fused = !(cx.flags & OFMK_F_SEPARATE_DETECT);
-    for (int f0 = 0; f0 < n; f0 += ws.frames) {
-        const int cf = n - f0 < ws.frames ? n - f0 : ws.frames;
-        const uint8_t *pin = in + (size_t)f0 * fs;
-        uint8_t *pout = out + (size_t)f0 * fs;
-        int32_t *zc = counts ? counts + (size_t)f0 * L : nullptr;
-        if ((rc = launch_analyze_yuv420(pin, layout, cf, H, W, ws, cx, fused ? zc : nullptr, L))) return rc;
-        if ((rc = launch_mark_yuv420(pin, pout, layout, cf, H, W, wm, n_wm, wm_row ? wm_row + f0 : nullptr, alpha, ws, fused, cx))) return rc;
-        if (fused) {
-            if ((rc = finalize_detect(f0, cf, H, W, L, alpha, counts, bits, ws, true, cx))) return rc;
-        } else {
-            if ((rc = launch_analyze_yuv420(pout, layout, cf, H, W, ws, cx, zc, L))) return rc;
-            if ((rc = finalize_detect(f0, cf, H, W, L, alpha, counts, bits, ws, false, cx))) return rc;
+    return for_chunks(n, ws.frames, [&](int f0, int cf) {
+        if (!(cx.flags & OFMK_F_SEPARATE_DETECT)) {
+            if (int rc = embed_chunk_yuv420(in, out, layout, f0, cf, H, W, wm, n_wm, wm_row, alpha, ws, true, cx, counts, L)) return rc;
+            return finalize_detect(f0, cf, H, W, L, alpha, counts, bits, ws, true, cx);
         }
-    }
-    return OFMK_OK;
+        if (int rc = embed_chunk_yuv420(in, out, layout, f0, cf, H, W, wm, n_wm, wm_row, alpha, ws, false, cx)) return rc;
+        return detect_chunk_yuv420(out, layout, f0, cf, H, W, L, alpha, counts, bits, ws, cx);
+    });
 }
 
 // ---- DwtDctSvd codec on planar YUV 4:2:0: the rgb8 SVD calls' conventions, the yuv420 calls' layout ----------------------------
@@ -1242,10 +1180,8 @@ int ofmk_svd_embed_yuv420(const uint8_t *in, uint8_t *out, int layout, int n, in
     if ((rc = check_blk(blk))) return rc;
     if ((rc = check_planar(layout, H, W, in, out))) return rc;
     SvdArgs a;
-    memset(&a, 0, sizeof(a));
-    if ((rc = set_scales(a, scales, false))) return rc;
-    a.wm = wm; a.wm_row = wm_row; a.n_wm = n_wm; a.N = (int)((long long)H * W / 64); a.L = 1;
-    return launch_svd_planar(in, out, layout, n, H, W, SVD_EMBED, a, blk, make_ctx(stream, opts));
+    if ((rc = make_svd_args(a, H, W, scales, false, wm, n_wm, wm_row, 1, nullptr, nullptr, nullptr))) return rc;
+    return launch_svd_yuv420(in, out, layout, n, H, W, SVD_EMBED, blk, a, make_ctx(stream, opts));
 }
 
 // scales[1] <= 0: zeroed counts / bits, as ofmk_svd_detect_rgb8
@@ -1257,18 +1193,9 @@ int ofmk_svd_detect_yuv420(const uint8_t *in, int layout, int n, int H, int W, i
     if ((rc = check_blk(blk))) return rc;
     if ((rc = check_planar(layout, H, W, in, nullptr))) return rc;
     SvdArgs a;
-    memset(&a, 0, sizeof(a));
-    if ((rc = set_scales(a, scales, true))) return rc;
-    if ((rc = check_partial(opts, L, counts, a.partial))) return rc;
-    a.counts = counts; a.bits = bits; a.N = (int)((long long)H * W / 64); a.L = L;
-    if (!(a.scales[1] > 0.f)) {
-        hipStream_t s = static_cast<hipStream_t>(stream);
-        const size_t bits_per_frame = blk == 8 ? (size_t)((long long)H * W / 256) : (size_t)a.N;
-        if (counts) HIP_TRY(launch_zero(counts, (size_t)n * L * sizeof(int32_t) * (a.partial ? (size_t)svd_count_tiles(H, W, blk) : 1), s));
-        if (bits) HIP_TRY(launch_zero(bits, (size_t)n * bits_per_frame, s));
-        return OFMK_OK;
-    }
-    return launch_svd_planar(in, nullptr, layout, n, H, W, SVD_DETECT, a, blk, make_ctx(stream, opts));
+    if ((rc = make_svd_args(a, H, W, scales, true, nullptr, 0, nullptr, L, counts, bits, opts))) return rc;
+    if (!(a.scales[1] > 0.f)) return zero_svd_readout(n, H, W, blk, a, static_cast<hipStream_t>(stream));
+    return launch_svd_yuv420(in, nullptr, layout, n, H, W, SVD_DETECT, blk, a, make_ctx(stream, opts));
 }
 
 int ofmk_svd_embed_detect_yuv420(const uint8_t *in, uint8_t *out, int layout, int n, int H, int W, const uint8_t *wm, int n_wm,
@@ -1281,52 +1208,16 @@ int ofmk_svd_embed_detect_yuv420(const uint8_t *in, uint8_t *out, int layout, in
     if ((rc = check_detect_args(out, n, H, W, L, counts, bits))) return rc;
     if ((rc = check_planar(layout, H, W, in, out))) return rc;
     SvdArgs a;
-    memset(&a, 0, sizeof(a));
-    if ((rc = set_scales(a, scales, false))) return rc;
-    if ((rc = check_partial(opts, L, counts, a.partial))) return rc;
-    a.wm = wm; a.wm_row = wm_row; a.n_wm = n_wm; a.counts = counts; a.bits = bits;
-    a.N = (int)((long long)H * W / 64); a.L = L;
-    return launch_svd_planar(in, out, layout, n, H, W, SVD_EMBED_VERIFY, a, blk, make_ctx(stream, opts));
+    if ((rc = make_svd_args(a, H, W, scales, false, wm, n_wm, wm_row, L, counts, bits, opts))) return rc;
+    return launch_svd_yuv420(in, out, layout, n, H, W, SVD_EMBED_VERIFY, blk, a, make_ctx(stream, opts));
 }
 
 int ofmk_yuv420_to_rgb8(const uint8_t *yuv, uint8_t *rgb, int layout, int n, int H, int W, void *stream, const ofmk_opts *opts) {
-    if (int orc = check_opts(opts)) return orc;
-    int rc = check_dims(n, H, W);
-    if (rc) return rc;
-    if (!yuv || !rgb) return fail(OFMK_E_ARG, "null pointer%s");
-    if ((rc = check_planar(layout, H, W, yuv, rgb))) return rc;
-    const PGeom g = make_pgeom(layout, H, W, 0);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    for (int f0 = 0; f0 < n; f0 += kMaxChunk) {
-        const int cf = n - f0 < kMaxChunk ? n - f0 : kMaxChunk;
-        const dim3 grid((unsigned)((g.nblk + kThreads - 1) / kThreads), (unsigned)cf);
-        const uint8_t *pi = yuv + (size_t)f0 * g.frame_stride;
-        uint8_t *po = rgb + (size_t)f0 * H * W * 3;
-        if (layout == OFMK_YUV_I420) hipLaunchKernelGGL(yuv420_to_rgb8_kernel<FMT_I420>, grid, dim3(kThreads), 0, s, pi, po, g);
-        else hipLaunchKernelGGL(yuv420_to_rgb8_kernel<FMT_NV12>, grid, dim3(kThreads), 0, s, pi, po, g);
-    }
-    HIP_TRY(hipGetLastError());
-    return OFMK_OK;
+    return convert_yuv420(const_cast<uint8_t *>(yuv), rgb, true, layout, n, H, W, stream, opts);
 }
 
 int ofmk_rgb8_to_yuv420(const uint8_t *rgb, uint8_t *yuv, int layout, int n, int H, int W, void *stream, const ofmk_opts *opts) {
-    if (int orc = check_opts(opts)) return orc;
-    int rc = check_dims(n, H, W);
-    if (rc) return rc;
-    if (!yuv || !rgb) return fail(OFMK_E_ARG, "null pointer%s");
-    if ((rc = check_planar(layout, H, W, yuv, rgb))) return rc;
-    const PGeom g = make_pgeom(layout, H, W, 0);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    for (int f0 = 0; f0 < n; f0 += kMaxChunk) {
-        const int cf = n - f0 < kMaxChunk ? n - f0 : kMaxChunk;
-        const dim3 grid((unsigned)((g.nblk + kThreads - 1) / kThreads), (unsigned)cf);
-        const uint8_t *pi = rgb + (size_t)f0 * H * W * 3;
-        uint8_t *po = yuv + (size_t)f0 * g.frame_stride;
-        if (layout == OFMK_YUV_I420) hipLaunchKernelGGL(rgb8_to_yuv420_kernel<FMT_I420>, grid, dim3(kThreads), 0, s, pi, po, g);
-        else hipLaunchKernelGGL(rgb8_to_yuv420_kernel<FMT_NV12>, grid, dim3(kThreads), 0, s, pi, po, g);
-    }
-    HIP_TRY(hipGetLastError());
-    return OFMK_OK;
+    return convert_yuv420(yuv, const_cast<uint8_t *>(rgb), false, layout, n, H, W, stream, opts);
 }
 
 int ofmk_probe_xcc(int32_t *xcc_of_workgroup, int n_workgroups, void *stream, const ofmk_opts *opts) {
