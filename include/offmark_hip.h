@@ -239,6 +239,35 @@ int ofmk_svd_detect_yuv420(const uint8_t *in, int layout, int n, int H, int W, i
 int ofmk_svd_embed_detect_yuv420(const uint8_t *in, uint8_t *out, int layout, int n, int H, int W,
                                  const uint8_t *wm, int n_wm, const int32_t *wm_row, const double *scales, int blk,
                                  int L, int32_t *counts, uint8_t *bits, void *stream, const ofmk_opts *opts);
+/* ---- C differently marked copies of the same 4:2:0 frames in one pass: the copies calls above on planes -----------------------
+ * The workflow the copies calls serve (tests/mark_video_to_hls.py:331-342) gets its frames from a decoder and hands them to an
+ * encoder, so they arrive and leave as 4:2:0 planes.  These calls read the planes once, do what does not depend on the watermark
+ * bit once (DCT: analyze's records, and every pixel's planes -> RGB -> Y / U / V conversion; DwtDctSvd: the LL band and top singular
+ * triple per tile) and write every copy: 1.5 + 1.5 * copies bytes per pixel (csrc/planar_copies_kernels.hiph).
+ *   in       device u8 [n] frames of 1.5*H*W bytes, `layout` as ofmk_*_yuv420
+ *   out      device u8 [copies][n][1.5*H*W], copy-major, the same layout as `in`; must not overlap `in` (OFMK_E_ARG)
+ *   copies   1..16;  wm_rows  device int32 [copies][n], clamped into [0, n_wm); NULL = copy c uses row c (clamped) for every frame
+ * Exact semantics, byte for byte:
+ *   ofmk_embed_copies_yuv420: copy c == ofmk_embed_yuv420(in, layout, wm, n_wm, wm_rows + c*n, alpha).  `chunk_frames` / `workspace`
+ *     as ofmk_embed_yuv420: the records are shared by all copies, ofmk_workspace_bytes(chunk, H, W) is all it needs (less than
+ *     ofmk_workspace_bytes(1, H, W): OFMK_E_WORKSPACE).  Launches are timed as kind 5 (planar analyze, once per chunk) and
+ *     6 (planar mark, every copy of the chunk in one launch).
+ *   ofmk_svd_embed_copies_yuv420: copy c == ofmk_svd_embed_yuv420(in, layout, wm, n_wm, wm_rows + c*n, scales, blk), with blk 8 the
+ *     fringe's 4:2:0 round trip included in every copy.  With `counts` or `bits` (verify; L >= 1): the counts and bits of copy c are
+ *     what ofmk_svd_embed_detect_yuv420 returns for that copy (by that function's contract, ofmk_svd_detect_yuv420 of the copy):
+ *     counts [copies][n][L], or with OFMK_F_PARTIAL_COUNTS [copies][n][tiles][L] (tiles = ofmk_svd_count_tiles(H, W, blk),
+ *     L <= 2048, counts non-null); bits [copies][n][bits per frame] (H*W/64 for blk 4, H*W/256 for blk 8).  Both NULL: no verify,
+ *     L is ignored.  blk 4 runs one fused copies kernel; blk 8 runs the single-copy launches once per copy (the same results, no
+ *     saving).  Launches are timed as kind 4 (svd).
+ *   With copies == 1 each call equals its single-copy counterpart; no result depends on chunk_frames or the workspace size.
+ *   Arguments are checked before any HIP call (OFMK_E_ARG): as the single-copy planar calls (layout, H and W multiples of 8,
+ *   8-byte aligned buffers, scales, blk, L, partial counts), plus the range of copies and the overlap of out with in. */
+int ofmk_embed_copies_yuv420(const uint8_t *in, uint8_t *out, int layout, int copies, int n, int H, int W,
+                             const uint8_t *wm, int n_wm, const int32_t *wm_rows, double alpha,
+                             int chunk_frames, void *workspace, size_t workspace_bytes, void *stream, const ofmk_opts *opts);
+int ofmk_svd_embed_copies_yuv420(const uint8_t *in, uint8_t *out, int layout, int copies, int n, int H, int W,
+                                 const uint8_t *wm, int n_wm, const int32_t *wm_rows, const double *scales, int blk,
+                                 int L, int32_t *counts, uint8_t *bits, void *stream, const ofmk_opts *opts);
 int ofmk_yuv420_to_rgb8(const uint8_t *yuv, uint8_t *rgb, int layout, int n, int H, int W, void *stream,
                         const ofmk_opts *opts);
 int ofmk_rgb8_to_yuv420(const uint8_t *rgb, uint8_t *yuv, int layout, int n, int H, int W, void *stream,

@@ -46,6 +46,7 @@
 #include "planar_kernels.hiph"
 #include "svd_planar_kernels.hiph"
 #include "copies_kernels.hiph"
+#include "planar_copies_kernels.hiph"
 
 namespace {
 
@@ -766,10 +767,11 @@ int launch_svd_yuv420(const uint8_t *in, uint8_t *out, int layout, int n, int H,
 // ---- C marked copies of the same frames (copies_kernels.hiph) -------------------------------------------------------
 constexpr int kMaxCopies = 16;       // a payload's copy field has 4 bits (fingerprint.payload_for_segment)
 
-// The argument checks every copies call shares: copies in range, out ([copies][n][H][W][3]) not overlapping in ([n][H][W][3]).
-int check_copies(const void *in, const void *out, int copies, int n, int H, int W) {
+// The argument checks every copies call shares: copies in range, out ([copies][n] frames of frame_bytes: H*W*3 as RGB, H*W*3/2
+// as 4:2:0 planes) not overlapping in ([n] frames).
+int check_copies(const void *in, const void *out, int copies, int n, size_t frame_bytes) {
     if (copies < 1 || copies > kMaxCopies) return fail(OFMK_E_ARG, "copies must be in [1, 16]%s");
-    const size_t fb = (size_t)n * H * W * 3;
+    const size_t fb = (size_t)n * frame_bytes;
     const uintptr_t i0 = (uintptr_t)in, o0 = (uintptr_t)out;
     if (o0 < i0 + fb && i0 < o0 + fb * (size_t)copies) return fail(OFMK_E_ARG, "out must not overlap in (no in-place copies)%s");
     return OFMK_OK;
@@ -801,6 +803,49 @@ int launch_svd_copies_rgb8(const uint8_t *in, uint8_t *out, int copies, int n, i
     });
     if (rc) return rc;
     return launch_copy_fringe_copies(in, out, copies, n, H, W, cx.s);
+}
+
+// The same on 4:2:0 planes (planar_copies_kernels.hiph).  One chunk of frames [f0, f0+cf) after launch_analyze_yuv420 left their
+// records in ws: every copy of them in one launch.
+int launch_mark_copies_yuv420(const uint8_t *in, uint8_t *out, int layout, int copies, int n, int f0, int cf, int H, int W,
+                              const uint8_t *wm, int n_wm, const int32_t *wm_rows, double alpha, const Workspace &ws, const Ctx &cx) {
+    const PGeom g = make_pgeom(layout, H, W, ws.plane);
+    const MarkArgs m = mark_args(ws, H, W, wm, n_wm, nullptr, alpha);
+    CopyArgs k;
+    memset(&k, 0, sizeof(k));
+    k.copies = copies;
+    k.rows_stride = n;
+    k.wm_rows = wm_rows ? wm_rows + f0 : nullptr;
+    k.out_stride = (size_t)n * g.frame_stride;
+    const size_t fo = (size_t)f0 * g.frame_stride;
+    ScopedTiming timing(KIND_PLANAR_MARK, cx);
+    with_fmt(layout, [&](auto fmt) {
+        OFMK_TIMED_LAUNCH(timing, mark_copies_yuv420_kernel<decltype(fmt)::value>, grid_2d(g.nblk, cf), dim3(kThreads), 0, cx.s, in + fo, out + fo, g, m, k);
+    });
+    HIP_TRY(hipGetLastError());
+    return OFMK_OK;
+}
+
+// blk = 4 on planes: every copy from one launch per kMaxChunk frames, as launch_svd_copies_rgb8 (H and W multiples of 8: no fringe).
+int launch_svd_copies_yuv420(const uint8_t *in, uint8_t *out, int layout, int copies, int n, int H, int W, const int32_t *wm_rows,
+                             const SvdArgs &a, const Ctx &cx) {
+    const PGeom g = make_pgeom(layout, H, W, 0);
+    const bool verify = a.counts || a.bits;
+    CopyArgs k;
+    memset(&k, 0, sizeof(k));
+    k.copies = copies;
+    k.rows_stride = n;
+    k.out_stride = (size_t)n * g.frame_stride;
+    k.counts_stride = (size_t)n * a.L * (a.partial ? (size_t)svd_count_tiles(H, W, 4) : 1);
+    k.bits_stride = (size_t)n * a.N;
+    return launch_svd({g.nblk, a.N, g.frame_stride, copies}, n, a, cx, [&](SvdChunk &c) {
+        CopyArgs kc = k;
+        kc.wm_rows = wm_rows ? wm_rows + c.f0 : nullptr;
+        with_fmt(layout, [&](auto fmt) { with_bool(verify, [&](auto vf) { with_bool(c.multi, [&](auto mu) {
+            OFMK_TIMED_LAUNCH(c.timing, (svd_copies_yuv420_kernel<decltype(fmt)::value, decltype(vf)::value, decltype(mu)::value>), c.grid, dim3(kThreads), 0, cx.s,
+                              in + c.offset, out + c.offset, g, c.frames, c.a, kc);
+        }); }); });
+    });
 }
 
 }  // namespace
@@ -996,7 +1041,7 @@ int ofmk_embed_copies_rgb8(const uint8_t *in, uint8_t *out, int copies, int n, i
     if (int orc = check_opts(opts)) return orc;
     int rc = check_embed_args(in, out, n, H, W, wm, n_wm);
     if (rc) return rc;
-    if ((rc = check_copies(in, out, copies, n, H, W))) return rc;
+    if ((rc = check_copies(in, out, copies, n, (size_t)H * W * 3))) return rc;
     Workspace ws;
     if ((rc = carve(workspace, workspace_bytes, H, W, chunk_frames, ws))) return rc;
     const Ctx cx = make_ctx(stream, opts);
@@ -1014,7 +1059,7 @@ int ofmk_svd_embed_copies_rgb8(const uint8_t *in, uint8_t *out, int copies, int 
     if (int orc = check_opts(opts)) return orc;
     int rc = check_embed_args(in, out, n, H, W, wm, n_wm);
     if (rc) return rc;
-    if ((rc = check_copies(in, out, copies, n, H, W))) return rc;
+    if ((rc = check_copies(in, out, copies, n, (size_t)H * W * 3))) return rc;
     if ((rc = check_blk(blk))) return rc;
     SvdArgs a;
     if ((rc = make_svd_args(a, H, W, scales, false, wm, n_wm, nullptr, L, counts, bits, opts))) return rc;
@@ -1210,6 +1255,57 @@ int ofmk_svd_embed_detect_yuv420(const uint8_t *in, uint8_t *out, int layout, in
     SvdArgs a;
     if ((rc = make_svd_args(a, H, W, scales, false, wm, n_wm, wm_row, L, counts, bits, opts))) return rc;
     return launch_svd_yuv420(in, out, layout, n, H, W, SVD_EMBED_VERIFY, blk, a, make_ctx(stream, opts));
+}
+
+// ---- C marked copies on planar YUV 4:2:0 (planar_copies_kernels.hiph) ----------------------------------------------------------
+int ofmk_embed_copies_yuv420(const uint8_t *in, uint8_t *out, int layout, int copies, int n, int H, int W, const uint8_t *wm, int n_wm,
+                             const int32_t *wm_rows, double alpha, int chunk_frames, void *workspace, size_t workspace_bytes,
+                             void *stream, const ofmk_opts *opts) {
+    if (int orc = check_opts(opts)) return orc;
+    int rc = check_embed_args(in, out, n, H, W, wm, n_wm);
+    if (rc) return rc;
+    if ((rc = check_planar(layout, H, W, in, out))) return rc;
+    if ((rc = check_copies(in, out, copies, n, (size_t)H * W * 3 / 2))) return rc;
+    Workspace ws;
+    if ((rc = carve(workspace, workspace_bytes, H, W, chunk_frames, ws))) return rc;
+    const Ctx cx = make_ctx(stream, opts);
+    return for_chunks(n, ws.frames, [&](int f0, int cf) {      // one analysis per chunk serves every copy
+        if (int rc = launch_analyze_yuv420(in + (size_t)f0 * H * W * 3 / 2, layout, cf, H, W, ws, cx)) return rc;
+        return launch_mark_copies_yuv420(in, out, layout, copies, n, f0, cf, H, W, wm, n_wm, wm_rows, alpha, ws, cx);
+    });
+}
+
+int ofmk_svd_embed_copies_yuv420(const uint8_t *in, uint8_t *out, int layout, int copies, int n, int H, int W, const uint8_t *wm,
+                                 int n_wm, const int32_t *wm_rows, const double *scales, int blk, int L, int32_t *counts,
+                                 uint8_t *bits, void *stream, const ofmk_opts *opts) {
+    if (int orc = check_opts(opts)) return orc;
+    int rc = check_embed_args(in, out, n, H, W, wm, n_wm);
+    if (rc) return rc;
+    if ((rc = check_blk(blk))) return rc;
+    if ((rc = check_planar(layout, H, W, in, out))) return rc;
+    const size_t fs = (size_t)H * W * 3 / 2;
+    if ((rc = check_copies(in, out, copies, n, fs))) return rc;
+    SvdArgs a;
+    if ((rc = make_svd_args(a, H, W, scales, false, wm, n_wm, nullptr, L, counts, bits, opts))) return rc;
+    const Ctx cx = make_ctx(stream, opts);
+    if (blk == 4) return launch_svd_copies_yuv420(in, out, layout, copies, n, H, W, wm_rows, a, cx);
+    // blk = 8: the single-copy launches (tiles, then the fringe's 4:2:0 round trip) once per copy, as ofmk_svd_embed_copies_rgb8
+    const int mode = counts || bits ? SVD_EMBED_VERIFY : SVD_EMBED;
+    const size_t count_rows = a.partial ? (size_t)svd_count_tiles(H, W, 8) : 1;
+    const size_t bits8 = (size_t)((long long)H * W / 256);
+    for (int q = 0; q < copies; ++q) {
+        SvdArgs b = a;
+        if (wm_rows) {
+            b.wm_row = wm_rows + (size_t)q * n;
+        } else {                                      // row q (clamped) for every frame: that row as a one-row table
+            b.wm = wm + (size_t)(q < n_wm - 1 ? q : n_wm - 1) * a.N;
+            b.n_wm = 1;
+        }
+        if (b.counts) b.counts += (size_t)q * n * a.L * count_rows;
+        if (b.bits) b.bits += (size_t)q * n * bits8;
+        if ((rc = launch_svd_yuv420(in, out + (size_t)q * n * fs, layout, n, H, W, mode, 8, b, cx))) return rc;
+    }
+    return OFMK_OK;
 }
 
 int ofmk_yuv420_to_rgb8(const uint8_t *yuv, uint8_t *rgb, int layout, int n, int H, int W, void *stream, const ofmk_opts *opts) {

@@ -94,3 +94,9 @@ class DctEncoder:
         with the build-defined BT.601 conversion fused into the kernels.  Returns marked planes of the same layout."""
         wm = wm_table if wm_table is not None else self._device_wm(height * width // 64)
         return self.engine.embed_yuv420(planes, height, width, wm, alpha=self.alpha, wm_row=wm_rows, out=out, layout=layout)
+
+    def encode_copies_planes_yuv420(self, planes, height, width, wm_rows, wm_table, out=None, layout="i420"):
+        """planes: CUDA uint8 [n, 1.5*H*W]; wm_rows: [C, n] rows of ``wm_table`` per copy and frame.  Returns the C marked copies
+        [C, n, 1.5*H*W] in one pass (the planes are read, analyzed and converted once); copy c equals
+        encode_planes_yuv420(planes, height, width, wm_rows=wm_rows[c], wm_table=wm_table) byte for byte."""
+        return self.engine.embed_copies_yuv420(planes, height, width, wm_table, wm_rows, alpha=self.alpha, out=out, layout=layout)

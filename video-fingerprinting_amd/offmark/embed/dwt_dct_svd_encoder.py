@@ -107,3 +107,18 @@ class DwtDctSvdEncoder:
         wm = wm_table if wm_table is not None else self._device_wm(height * width // 64)
         return self.engine.svd_embed_yuv420(planes, height, width, wm, scales=self._scales, wm_row=wm_rows, out=out, blk=self.blk,
                                             layout=layout)
+
+    def encode_copies_planes_yuv420(self, planes, height, width, wm_rows, wm_table, out=None, layout="i420"):
+        """planes: CUDA uint8 [n, 1.5*H*W]; wm_rows: [C, n] rows of ``wm_table`` per copy and frame.  Returns the C marked copies
+        [C, n, 1.5*H*W] in one pass (one LL band and SVD per tile serve every copy); copy c equals
+        encode_planes_yuv420(planes, height, width, wm_rows=wm_rows[c], wm_table=wm_table) byte for byte."""
+        return self.engine.svd_embed_copies_yuv420(planes, height, width, wm_table, wm_rows, scales=self._scales, blk=self.blk,
+                                                   out=out, layout=layout)
+
+    def encode_verify_copies_planes_yuv420(self, planes, height, width, wm_rows, wm_table, payload_len, out=None, layout="i420"):
+        """encode_copies_planes_yuv420 plus the read-out of every written copy with this encoder's channel-1 scale and blk:
+        returns (copies [C, n, 1.5*H*W], counts int32 [C, n, payload_len]); counts[c] equals what a DwtDctSvdDecoder with the
+        same channel-1 scale and blk returns from decode_planes_yuv420(copies[c], height, width, payload_len)."""
+        out, counts, _ = self.engine.svd_embed_copies_yuv420(planes, height, width, wm_table, wm_rows, scales=self._scales,
+                                                             blk=self.blk, out=out, L=int(payload_len), layout=layout)
+        return out, counts

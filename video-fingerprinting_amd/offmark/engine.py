@@ -628,6 +628,57 @@ class DctEngine:
                                                          self._o(extra_flags=flag)))
         return out, counts, bits
 
+    # -- C marked copies of the same 4:2:0 frames in one pass (csrc/planar_copies_kernels.hiph) ------------------------------
+    def embed_copies_yuv420(self, planes, H, W, wm, wm_rows, alpha=20, out=None, copies=None, layout="i420"):
+        """C differently marked copies of frames given as 4:2:0 planes [n, 1.5*H*W] in one pass: uint8 [C, n, 1.5*H*W] of the same
+        layout whose copy c equals, byte for byte, ``embed_yuv420(planes, H, W, wm, alpha, wm_row=wm_rows[c])``.  wm_rows as
+        embed_copies.  The frames are analyzed and converted once for all copies."""
+        n = self._check_planar(planes, H, W)
+        fmt = self._layout(layout)
+        wm = self._wm(wm, H * W // 64)
+        rows, C = self._copy_rows(wm_rows, n, wm.shape[0], copies)
+        out = self._out(out, planes, (C, n, H * W * 3 // 2))
+        cf = self._chunk(n, H, W)
+        ws = self.workspace(H, W, cf)
+        _hip.check(self.lib.ofmk_embed_copies_yuv420(planes.data_ptr(), out.data_ptr(), fmt, C, n, H, W, wm.data_ptr(), wm.shape[0],
+                                                     _hip.ptr(rows), float(alpha), cf, ws.data_ptr(), ws.numel(),
+                                                     _hip.current_stream(), self._o()))
+        return out
+
+    def svd_embed_copies_yuv420(self, planes, H, W, wm, wm_rows, scale=15, scales=None, blk=4, out=None, L=None, want_bits=False,
+                                counts=None, partial=False, copies=None, layout="i420"):
+        """The DwtDctSvd codec's copies on 4:2:0 planes in one pass: copy c of the uint8 [C, n, 1.5*H*W] result equals
+        ``svd_embed_yuv420`` with ``wm_row=wm_rows[c]``.  With ``L``: also the verify of every copy, returns (out, counts [C, n, L]
+        -- or, ``partial``, [C, n, tiles, L] -- and bits [C, n, bits_per_frame] or None), each copy's equal to
+        ``svd_embed_detect_yuv420``'s."""
+        t = self.torch
+        n = self._check_planar(planes, H, W)
+        fmt = self._layout(layout)
+        wm = self._wm(wm, H * W // 64)
+        rows, C = self._copy_rows(wm_rows, n, wm.shape[0], copies)
+        out = self._out(out, planes, (C, n, H * W * 3 // 2))
+        flag, bits = 0, None
+        if L is not None:
+            if partial:
+                tiles = int(self.lib.ofmk_svd_count_tiles(H, W, int(blk)))
+                if tiles < 0:
+                    raise _hip.HipError(f"bad frame size or blk ({H}x{W}, blk={blk})")
+                shape, flag = (C, n, tiles, int(L)), _hip.F_PARTIAL_COUNTS
+            else:
+                shape = (C, n, int(L))
+            if counts is None:
+                counts = t.empty(shape, dtype=t.int32, device=self.device)
+            elif not (isinstance(counts, t.Tensor) and counts.is_cuda and counts.device == self.device and counts.dtype == t.int32
+                      and tuple(counts.shape) == shape and counts.is_contiguous()):
+                raise ValueError(f"counts must be a contiguous CUDA int32 tensor of shape {shape} on {self.device}")
+            if want_bits:
+                bits = t.empty((C, n, self.svd_bits_per_frame(H, W, blk)), dtype=t.uint8, device=self.device)
+        _hip.check(self.lib.ofmk_svd_embed_copies_yuv420(planes.data_ptr(), out.data_ptr(), fmt, C, n, H, W, wm.data_ptr(),
+                                                         wm.shape[0], _hip.ptr(rows), _hip.scales3(scale, scales), int(blk),
+                                                         int(L) if L is not None else 0, _hip.ptr(counts) if L is not None else None,
+                                                         _hip.ptr(bits), _hip.current_stream(), self._o(extra_flags=flag)))
+        return out if L is None else (out, counts, bits)
+
     def svd_encode_yuv(self, yuv, wm, scale=15, scales=None, blk=4):
         t = self.torch
         n, H, W = self._check_frames(yuv, t.float32)

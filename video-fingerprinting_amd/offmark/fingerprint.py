@@ -84,7 +84,7 @@ def identify_copies(segment_votes: dict, segment_numbers=None) -> list[int | Non
 # ---------------------------------------------------------------------------------------------
 # Marking N copies per segment, verifying them, and the reference's JSON sidecars
 # (tests/mark_video_to_hls.py:330-434).  The pixel work is one batched GPU call for all copies when the encoder offers
-# encode_copies_u8, else one per copy.
+# encode_copies_u8 (RGB frames) / encode_copies_planes_yuv420 (4:2:0 planes), else one per copy.
 # ---------------------------------------------------------------------------------------------
 
 def _reads_like(encoder, decoder) -> bool:
@@ -95,18 +95,11 @@ def _reads_like(encoder, decoder) -> bool:
             and getattr(encoder, "_scales", [None] * 3)[1] == decoder._scales[1])
 
 
-def mark_segment_copies(encoder, decoder, frames, segment_of_frame, num_copies: int, key=0, min_frequency: float = 0.5):
-    """Mark ``num_copies`` versions of every segment and verify each one.
-
-    encoder / decoder: HIP codecs offering ``encode_frames_u8`` / ``decode_frames_u8`` (DctEncoder+DctDecoder or
-    DwtDctSvdEncoder+DwtDctSvdDecoder).  frames: CUDA uint8 [n, H, W, 3]; segment_of_frame: int array [n].
-    Returns (copies, sidecars): copies[c] is the marked tensor of copy c; sidecars holds the dicts the
-    reference writes as segment_payloads.json / segment_copies.json / failed_segments.json, with the same
-    keys.  A copy fails verification when its per-segment vote differs from its payload or the winning
-    pattern covers fewer than ``min_frequency`` of the frames (mark_video_to_hls.py:381).
-    An encoder offering ``encode_copies_u8`` marks all copies (up to 16) in one pass, and copies[c] are views of its result;
-    a DwtDctSvdEncoder whose decoder reads with the same channel-1 scale and blk also hands over the verify's counts
-    (``encode_verify_copies_u8``).  Copies and sidecars are the same either way."""
+def _mark_copies(device, n, H, W, n_bits, segment_of_frame, num_copies, key, min_frequency, one_pass, one_copy, read):
+    """The bookkeeping mark_segment_copies and mark_segment_copies_yuv420 share: watermark table and rows of every (segment, copy),
+    the marking (``one_pass(rows_dev [C, n], table_dev)`` -> (marked [C, ...], counts [C, n, 8] or None), or None when the
+    encoder has no one-pass call; then ``one_copy(rows_dev [n], table_dev)`` per copy), the vote of every copy
+    (``read(marked)`` -> counts where the marking left none) and the sidecar dicts."""
     import torch
     from .degenerator.de_shuffler import DeShuffler
     from .dist.vote import vote_segments
@@ -114,31 +107,24 @@ def mark_segment_copies(encoder, decoder, frames, segment_of_frame, num_copies: 
 
     seg = np.asarray(segment_of_frame)
     segments = [int(s) for s in np.unique(seg)]
-    n, H, W, _ = frames.shape
     N = H * W // 64
     gen = Shuffler(key=key)
     deg = DeShuffler(key=key).set_shape((8,))
     index = {(s, c): i for i, (s, c) in enumerate((s, c) for s in segments for c in range(num_copies))}
     table = np.stack([gen.generate_wm(payload_for_segment(s, c), (N,)) for s in segments for c in range(num_copies)])
-    table_dev = torch.from_numpy(table.astype(np.uint8)).to(frames.device)
+    table_dev = torch.from_numpy(table.astype(np.uint8)).to(device)
     copies, segment_payloads, failed = [], {}, []
     segment_copies = {str(s): [] for s in segments}
-    n_bits = decoder.bits_per_frame(H, W) if hasattr(decoder, "bits_per_frame") else N      # DwtDctSvd(blk=8): H*W//256
     rows_all = np.array([[index[(int(s), c)] for s in seg] for c in range(num_copies)], dtype=np.int32).reshape(num_copies, n)
     marked_all = counts_all = None
-    if hasattr(encoder, "encode_copies_u8") and 1 <= num_copies <= 16:
-        # one pass for every copy: the frames are read and analyzed once (csrc/copies_kernels.hiph)
-        rows_dev = torch.from_numpy(rows_all).to(frames.device)
-        if hasattr(encoder, "encode_verify_copies_u8") and _reads_like(encoder, decoder):
-            marked_all, counts_all = encoder.encode_verify_copies_u8(frames, rows_dev, table_dev, 8)
-        else:
-            marked_all = encoder.encode_copies_u8(frames, rows_dev, table_dev)
+    if one_pass is not None and 1 <= num_copies <= 16:
+        marked_all, counts_all = one_pass(torch.from_numpy(rows_all).to(device), table_dev)
     for c in range(num_copies):
         if marked_all is not None:
             marked = marked_all[c]
         else:
-            marked = encoder.encode_frames_u8(frames, wm_rows=torch.from_numpy(rows_all[c]).to(frames.device), wm_table=table_dev)
-        counts = counts_all[c] if counts_all is not None else decoder.decode_frames_u8(marked, 8)[0]
+            marked = one_copy(torch.from_numpy(rows_all[c]).to(device), table_dev)
+        counts = counts_all[c] if counts_all is not None else read(marked)
         votes = vote_segments(deg.degenerate_counts(counts.cpu().numpy(), n_bits), seg)
         copies.append(marked)
         for s in segments:
@@ -157,6 +143,56 @@ def mark_segment_copies(encoder, decoder, frames, segment_of_frame, num_copies: 
         "failed_segments": failed,
     }
     return copies, sidecars
+
+
+def mark_segment_copies(encoder, decoder, frames, segment_of_frame, num_copies: int, key=0, min_frequency: float = 0.5):
+    """Mark ``num_copies`` versions of every segment and verify each one.
+
+    encoder / decoder: HIP codecs offering ``encode_frames_u8`` / ``decode_frames_u8`` (DctEncoder+DctDecoder or
+    DwtDctSvdEncoder+DwtDctSvdDecoder).  frames: CUDA uint8 [n, H, W, 3]; segment_of_frame: int array [n].
+    Returns (copies, sidecars): copies[c] is the marked tensor of copy c; sidecars holds the dicts the
+    reference writes as segment_payloads.json / segment_copies.json / failed_segments.json, with the same
+    keys.  A copy fails verification when its per-segment vote differs from its payload or the winning
+    pattern covers fewer than ``min_frequency`` of the frames (mark_video_to_hls.py:381).
+    An encoder offering ``encode_copies_u8`` marks all copies (up to 16) in one pass, and copies[c] are views of its result;
+    a DwtDctSvdEncoder whose decoder reads with the same channel-1 scale and blk also hands over the verify's counts
+    (``encode_verify_copies_u8``).  Copies and sidecars are the same either way."""
+    n, H, W, _ = frames.shape
+    n_bits = decoder.bits_per_frame(H, W) if hasattr(decoder, "bits_per_frame") else H * W // 64      # DwtDctSvd(blk=8): H*W//256
+    one_pass = None
+    if hasattr(encoder, "encode_copies_u8"):
+        # one pass for every copy: the frames are read and analyzed once (csrc/copies_kernels.hiph)
+        def one_pass(rows_dev, table_dev):
+            if hasattr(encoder, "encode_verify_copies_u8") and _reads_like(encoder, decoder):
+                return encoder.encode_verify_copies_u8(frames, rows_dev, table_dev, 8)
+            return encoder.encode_copies_u8(frames, rows_dev, table_dev), None
+    return _mark_copies(frames.device, n, H, W, n_bits, segment_of_frame, num_copies, key, min_frequency, one_pass,
+                        lambda rows, table: encoder.encode_frames_u8(frames, wm_rows=rows, wm_table=table),
+                        lambda marked: decoder.decode_frames_u8(marked, 8)[0])
+
+
+def mark_segment_copies_yuv420(encoder, decoder, planes, height, width, segment_of_frame, num_copies: int, key=0,
+                               min_frequency: float = 0.5, layout="i420"):
+    """mark_segment_copies on 4:2:0 planes, what a video decoder hands over and an encoder takes: planes is CUDA uint8
+    [n, 1.5*H*W] (``layout``: "i420" or "nv12"), the encoder / decoder offer ``encode_planes_yuv420`` /
+    ``decode_planes_yuv420``.  Returns (copies, sidecars) with the same sidecar dicts; copies[c] are marked planes of the same
+    layout.  An encoder offering ``encode_copies_planes_yuv420`` marks all copies (up to 16) in one pass
+    (csrc/planar_copies_kernels.hiph) and copies[c] are views of one [C, n, 1.5*H*W] tensor; a DwtDctSvdEncoder whose decoder
+    reads with the same channel-1 scale and blk also hands over the verify's counts
+    (``encode_verify_copies_planes_yuv420``).  Otherwise one ``encode_planes_yuv420`` call per copy.  Copies and sidecars are
+    the same either way."""
+    n = planes.shape[0]
+    n_bits = decoder.bits_per_frame(height, width) if hasattr(decoder, "bits_per_frame") else height * width // 64
+    one_pass = None
+    if hasattr(encoder, "encode_copies_planes_yuv420"):
+        def one_pass(rows_dev, table_dev):
+            if hasattr(encoder, "encode_verify_copies_planes_yuv420") and _reads_like(encoder, decoder):
+                return encoder.encode_verify_copies_planes_yuv420(planes, height, width, rows_dev, table_dev, 8, layout=layout)
+            return encoder.encode_copies_planes_yuv420(planes, height, width, rows_dev, table_dev, layout=layout), None
+    return _mark_copies(planes.device, n, height, width, n_bits, segment_of_frame, num_copies, key, min_frequency, one_pass,
+                        lambda rows, table: encoder.encode_planes_yuv420(planes, height, width, wm_rows=rows, wm_table=table,
+                                                                         layout=layout),
+                        lambda marked: decoder.decode_planes_yuv420(marked, height, width, 8, layout=layout)[0])
 
 
 def write_sidecars(directory: str, sidecars: dict) -> list[str]:
