@@ -5,7 +5,9 @@ shows the command), one at each commit.  Kernels are compared per symbol, becaus
 of instantiation in the host code: the instruction text after removing assembler comments and the function number inside local
 labels (.LBB<k>_<i>, .Lfunc_end<k>), and vgpr / sgpr / scratch / LDS from the metadata.  The long-branch labels .Lpost_getpc<j> carry a
 serial number that runs through the whole listing, so it moves with the order of the kernels too: they are renumbered inside each
-kernel in order of appearance.  Exit status 0 = same set of kernels, all equal."""
+kernel in order of appearance.  For a change that may touch some kernels: every kernel whose text differs is listed with its
+instruction line count in A and in B, and the LDS / global / flat atomic instructions are counted per kernel family (the
+template's name) in A and in B.  Exit status 0 = same set of kernels, all equal."""
 import re
 import sys
 
@@ -28,6 +30,11 @@ def kernels(path):
     return meta, body
 
 
+def family(symbol):
+    m = re.match(r"_ZN4ofmk(\d+)", symbol)              # the kernel's name without its template arguments
+    return symbol[m.end():m.end() + int(m.group(1))] if m else symbol
+
+
 (ma, ba), (mb, bb) = kernels(sys.argv[1]), kernels(sys.argv[2])
 only_a, only_b = sorted(set(ma) - set(mb)), sorted(set(mb) - set(ma))
 both = sorted(set(ma) & set(mb))
@@ -38,6 +45,14 @@ print(f"instruction text differs: {text_differs}")
 print(f"{' / '.join(KEYS)} differ: {[(k, ma[k], mb[k]) for k in meta_differs]}")
 print(f"kernels with scratch: {[k for k in mb if mb[k][2]]}")
 print(f"instruction lines compared: {sum(b.count(chr(10)) + 1 for b in ba.values())}")
+for k in text_differs:
+    print(f"  {k}: {ba[k].count(chr(10)) + 1} -> {bb[k].count(chr(10)) + 1} instruction lines")
+print("atomic instructions per kernel family (kernels; ds_add / global_atomic / flat_atomic), A -> B:")
+for fam in sorted({family(k) for k in both}):
+    ks = [k for k in both if family(k) == fam]
+    na, nb = ([sum(len(re.findall(r"^\s*" + op, b[k], re.M)) for k in ks) for op in ("ds_add", "global_atomic", "flat_atomic")] for b in (ba, bb))
+    if any(na) or any(nb):
+        print(f"  {fam} ({len(ks)}): {na[0]} / {na[1]} / {na[2]} -> {nb[0]} / {nb[1]} / {nb[2]}")
 ok = not (only_a or only_b or text_differs or meta_differs)
 print("SAME DEVICE CODE" if ok else "DEVICE CODE DIFFERS")
 sys.exit(0 if ok else 1)

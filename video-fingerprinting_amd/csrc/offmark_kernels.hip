@@ -448,6 +448,22 @@ int detect_chunk(const void *in, int src, int f0, int cf, int H, int W, int L, d
     return finalize_detect(f0, cf, H, W, L, alpha, counts, bits, ws, false, s);
 }
 
+// The copies half of a copies kernel's arguments, for a launch that starts at frame f0 of the call's n: wm_rows is the call's
+// [copies][n] table or null, out the call's [copies][n] frames of frame_bytes.  DwtDctSvd verify: a copy's counts are
+// counts_per_frame int32 entries per frame (the DCT codec's copies have no read-out: 0), its bits bits_per_frame bytes.
+CopyArgs make_copy_args(int copies, int n, int f0, const int32_t *wm_rows, size_t frame_bytes, size_t counts_per_frame = 0,
+                        size_t bits_per_frame = 0) {
+    CopyArgs k;
+    memset(&k, 0, sizeof(k));
+    k.copies = copies;
+    k.rows_stride = n;
+    k.wm_rows = wm_rows ? wm_rows + f0 : nullptr;
+    k.out_stride = (size_t)n * frame_bytes;
+    k.counts_stride = (size_t)n * counts_per_frame;
+    k.bits_stride = (size_t)n * bits_per_frame;
+    return k;
+}
+
 // One chunk of frames [f0, f0+cf) after launch_analyze left their records in ws: every copy of them in one launch.
 int launch_mark_copies_rgb8(const uint8_t *in, uint8_t *out, int copies, int n, int f0, int cf, int H, int W, const uint8_t *wm,
                             int n_wm, const int32_t *wm_rows, double alpha, const Workspace &ws, const Ctx &cx) {
@@ -458,12 +474,7 @@ int launch_mark_copies_rgb8(const uint8_t *in, uint8_t *out, int copies, int n, 
     const Geom g = make_geom(H, W, ws, cf, xc);
     const dim3 grid = xcd_grid(g.nblk, cf, xc);
     const MarkArgs m = mark_args(ws, H, W, wm, n_wm, nullptr, alpha);
-    CopyArgs k;
-    memset(&k, 0, sizeof(k));
-    k.copies = copies;
-    k.rows_stride = n;
-    k.wm_rows = wm_rows ? wm_rows + f0 : nullptr;
-    k.out_stride = (size_t)n * fs;
+    const CopyArgs k = make_copy_args(copies, n, f0, wm_rows, fs);
     ScopedTiming timing(KIND_MARK, cx);
     with_bool(aligned_rows(in, W, 1) && aligned_rows(out, W, 1), [&](auto al) {     // frame and copy strides are multiples of 8 when W is
         OFMK_TIMED_LAUNCH(timing, mark_copies_rgb8_kernel<decltype(al)::value>, grid, dim3(kThreads), 0, cx.s, pin, pout, g, m, k);
@@ -767,6 +778,28 @@ int launch_svd_yuv420(const uint8_t *in, uint8_t *out, int layout, int n, int H,
 // ---- C marked copies of the same frames (copies_kernels.hiph) -------------------------------------------------------
 constexpr int kMaxCopies = 16;       // a payload's copy field has 4 bits (fingerprint.payload_for_segment)
 
+// blk = 8 has no fused copies kernel for its 16x16 tiles: the single-copy launches once per copy.  launch(out_q, a_q) is that
+// launcher on copy q's frames, with copy q's watermark rows, counts and bits.
+template <class Launch>
+int launch_svd8_copies(uint8_t *out, size_t frame_bytes, int copies, int n, int H, int W, const int32_t *wm_rows, const SvdArgs &a,
+                       Launch &&launch) {
+    const size_t count_rows = a.partial ? (size_t)svd_count_tiles(H, W, 8) : 1;
+    const size_t bits8 = (size_t)((long long)H * W / 256);
+    for (int q = 0; q < copies; ++q) {
+        SvdArgs b = a;
+        if (wm_rows) {
+            b.wm_row = wm_rows + (size_t)q * n;
+        } else {                                      // row q (clamped) for every frame: that row as a one-row table
+            b.wm = a.wm + (size_t)(q < a.n_wm - 1 ? q : a.n_wm - 1) * a.N;
+            b.n_wm = 1;
+        }
+        if (b.counts) b.counts += (size_t)q * n * a.L * count_rows;
+        if (b.bits) b.bits += (size_t)q * n * bits8;
+        if (int rc = launch(out + (size_t)q * n * frame_bytes, b)) return rc;
+    }
+    return OFMK_OK;
+}
+
 // The argument checks every copies call shares: copies in range, out ([copies][n] frames of frame_bytes: H*W*3 as RGB, H*W*3/2
 // as 4:2:0 planes) not overlapping in ([n] frames).
 int check_copies(const void *in, const void *out, int copies, int n, size_t frame_bytes) {
@@ -783,17 +816,10 @@ int launch_svd_copies_rgb8(const uint8_t *in, uint8_t *out, int copies, int n, i
                            const Ctx &cx) {
     const Geom g = svd_geom(H, W);
     const bool verify = a.counts || a.bits;
+    const size_t count_rows = a.partial ? (size_t)svd_count_tiles(H, W, 4) : 1;
     const bool al = aligned_rows(in, W, 1) && aligned_rows(out, W, 1);
-    CopyArgs k;
-    memset(&k, 0, sizeof(k));
-    k.copies = copies;
-    k.rows_stride = n;
-    k.out_stride = (size_t)n * g.frame_stride;
-    k.counts_stride = (size_t)n * a.L * (a.partial ? (size_t)svd_count_tiles(H, W, 4) : 1);
-    k.bits_stride = (size_t)n * a.N;
     int rc = launch_svd({g.nblk, a.N, g.frame_stride, copies}, n, a, cx, [&](SvdChunk &c) {
-        CopyArgs kc = k;
-        kc.wm_rows = wm_rows ? wm_rows + c.f0 : nullptr;
+        const CopyArgs kc = make_copy_args(copies, n, c.f0, wm_rows, g.frame_stride, count_rows * a.L, a.N);
         Geom gc = g;
         gc.frames = c.frames;
         with_bool(al, [&](auto al_) { with_bool(verify, [&](auto vf) { with_bool(c.multi, [&](auto mu) {
@@ -811,12 +837,7 @@ int launch_mark_copies_yuv420(const uint8_t *in, uint8_t *out, int layout, int c
                               const uint8_t *wm, int n_wm, const int32_t *wm_rows, double alpha, const Workspace &ws, const Ctx &cx) {
     const PGeom g = make_pgeom(layout, H, W, ws.plane);
     const MarkArgs m = mark_args(ws, H, W, wm, n_wm, nullptr, alpha);
-    CopyArgs k;
-    memset(&k, 0, sizeof(k));
-    k.copies = copies;
-    k.rows_stride = n;
-    k.wm_rows = wm_rows ? wm_rows + f0 : nullptr;
-    k.out_stride = (size_t)n * g.frame_stride;
+    const CopyArgs k = make_copy_args(copies, n, f0, wm_rows, g.frame_stride);
     const size_t fo = (size_t)f0 * g.frame_stride;
     ScopedTiming timing(KIND_PLANAR_MARK, cx);
     with_fmt(layout, [&](auto fmt) {
@@ -831,16 +852,9 @@ int launch_svd_copies_yuv420(const uint8_t *in, uint8_t *out, int layout, int co
                              const SvdArgs &a, const Ctx &cx) {
     const PGeom g = make_pgeom(layout, H, W, 0);
     const bool verify = a.counts || a.bits;
-    CopyArgs k;
-    memset(&k, 0, sizeof(k));
-    k.copies = copies;
-    k.rows_stride = n;
-    k.out_stride = (size_t)n * g.frame_stride;
-    k.counts_stride = (size_t)n * a.L * (a.partial ? (size_t)svd_count_tiles(H, W, 4) : 1);
-    k.bits_stride = (size_t)n * a.N;
+    const size_t count_rows = a.partial ? (size_t)svd_count_tiles(H, W, 4) : 1;
     return launch_svd({g.nblk, a.N, g.frame_stride, copies}, n, a, cx, [&](SvdChunk &c) {
-        CopyArgs kc = k;
-        kc.wm_rows = wm_rows ? wm_rows + c.f0 : nullptr;
+        const CopyArgs kc = make_copy_args(copies, n, c.f0, wm_rows, g.frame_stride, count_rows * a.L, a.N);
         with_fmt(layout, [&](auto fmt) { with_bool(verify, [&](auto vf) { with_bool(c.multi, [&](auto mu) {
             OFMK_TIMED_LAUNCH(c.timing, (svd_copies_yuv420_kernel<decltype(fmt)::value, decltype(vf)::value, decltype(mu)::value>), c.grid, dim3(kThreads), 0, cx.s,
                               in + c.offset, out + c.offset, g, c.frames, c.a, kc);
@@ -1066,23 +1080,8 @@ int ofmk_svd_embed_copies_rgb8(const uint8_t *in, uint8_t *out, int copies, int 
     const int mode = counts || bits ? SVD_EMBED_VERIFY : SVD_EMBED;
     const Ctx cx = make_ctx(stream, opts);
     if (blk == 4) return launch_svd_copies_rgb8(in, out, copies, n, H, W, wm_rows, a, cx);
-    // blk = 8: the single-copy launches once per copy (no fused copies kernel for 16x16 tiles)
-    const size_t fs = (size_t)H * W * 3;
-    const size_t count_rows = a.partial ? (size_t)svd_count_tiles(H, W, 8) : 1;
-    const size_t bits8 = (size_t)((long long)H * W / 256);
-    for (int q = 0; q < copies; ++q) {
-        SvdArgs b = a;
-        if (wm_rows) {
-            b.wm_row = wm_rows + (size_t)q * n;
-        } else {                                      // row q (clamped) for every frame: that row as a one-row table
-            b.wm = wm + (size_t)(q < n_wm - 1 ? q : n_wm - 1) * a.N;
-            b.n_wm = 1;
-        }
-        if (b.counts) b.counts += (size_t)q * n * a.L * count_rows;
-        if (b.bits) b.bits += (size_t)q * n * bits8;
-        if ((rc = launch_svd_rgb8(in, out + (size_t)q * n * fs, n, H, W, mode, 8, b, cx))) return rc;
-    }
-    return OFMK_OK;
+    return launch_svd8_copies(out, (size_t)H * W * 3, copies, n, H, W, wm_rows, a,
+                              [&](uint8_t *out_q, const SvdArgs &b) { return launch_svd_rgb8(in, out_q, n, H, W, mode, 8, b, cx); });
 }
 
 int ofmk_svd_encode_yuv32f(float *yuv, int n, int H, int W, const uint8_t *wm, int n_wm, const int32_t *wm_row,
@@ -1289,23 +1288,9 @@ int ofmk_svd_embed_copies_yuv420(const uint8_t *in, uint8_t *out, int layout, in
     if ((rc = make_svd_args(a, H, W, scales, false, wm, n_wm, nullptr, L, counts, bits, opts))) return rc;
     const Ctx cx = make_ctx(stream, opts);
     if (blk == 4) return launch_svd_copies_yuv420(in, out, layout, copies, n, H, W, wm_rows, a, cx);
-    // blk = 8: the single-copy launches (tiles, then the fringe's 4:2:0 round trip) once per copy, as ofmk_svd_embed_copies_rgb8
-    const int mode = counts || bits ? SVD_EMBED_VERIFY : SVD_EMBED;
-    const size_t count_rows = a.partial ? (size_t)svd_count_tiles(H, W, 8) : 1;
-    const size_t bits8 = (size_t)((long long)H * W / 256);
-    for (int q = 0; q < copies; ++q) {
-        SvdArgs b = a;
-        if (wm_rows) {
-            b.wm_row = wm_rows + (size_t)q * n;
-        } else {                                      // row q (clamped) for every frame: that row as a one-row table
-            b.wm = wm + (size_t)(q < n_wm - 1 ? q : n_wm - 1) * a.N;
-            b.n_wm = 1;
-        }
-        if (b.counts) b.counts += (size_t)q * n * a.L * count_rows;
-        if (b.bits) b.bits += (size_t)q * n * bits8;
-        if ((rc = launch_svd_yuv420(in, out + (size_t)q * n * fs, layout, n, H, W, mode, 8, b, cx))) return rc;
-    }
-    return OFMK_OK;
+    const int mode = counts || bits ? SVD_EMBED_VERIFY : SVD_EMBED;         // per copy: the tiles, then the fringe's 4:2:0 round trip
+    return launch_svd8_copies(out, fs, copies, n, H, W, wm_rows, a,
+                              [&](uint8_t *out_q, const SvdArgs &b) { return launch_svd_yuv420(in, out_q, layout, n, H, W, mode, 8, b, cx); });
 }
 
 int ofmk_yuv420_to_rgb8(const uint8_t *yuv, uint8_t *rgb, int layout, int n, int H, int W, void *stream, const ofmk_opts *opts) {

@@ -467,22 +467,26 @@ class DctEngine:
                                                 self._o()))
         return out
 
-    def _svd_counts(self, counts, n, H, W, L, blk, partial):
+    def _svd_counts(self, counts, n, H, W, L, blk, partial, copies=None):
         """The read-out's counts buffer: [n, L] (cleared by the library, added into with atomics) or, ``partial``, the
         per-workgroup form [n, tiles, L] the frame kernel stores in full -- no fill dispatch in front of it
-        (include/offmark_hip.h: OFMK_F_PARTIAL_COUNTS; L <= 2048); hand it to payloads() / counts_from_partial()."""
-        if not partial:
-            return self._counts(counts, n, L), 0
+        (include/offmark_hip.h: OFMK_F_PARTIAL_COUNTS; L <= 2048); hand it to payloads() / counts_from_partial().
+        ``copies``: one such buffer per copy, [copies, n, ...].  Returns (counts, the flag for the call's opts)."""
         t = self.torch
-        tiles = int(self.lib.ofmk_svd_count_tiles(H, W, int(blk)))
-        if tiles < 0:
-            raise _hip.HipError(f"bad frame size or blk ({H}x{W}, blk={blk})")
+        shape, flag = (n, int(L)), 0
+        if partial:
+            tiles = int(self.lib.ofmk_svd_count_tiles(H, W, int(blk)))
+            if tiles < 0:
+                raise _hip.HipError(f"bad frame size or blk ({H}x{W}, blk={blk})")
+            shape, flag = (n, tiles, int(L)), _hip.F_PARTIAL_COUNTS
+        if copies is not None:
+            shape = (copies,) + shape
         if counts is None:
-            counts = t.empty((n, tiles, L), dtype=t.int32, device=self.device)
-        elif not (isinstance(counts, t.Tensor) and counts.is_cuda and counts.dtype == t.int32 and tuple(counts.shape) == (n, tiles, L)
-                  and counts.is_contiguous()):
-            raise ValueError(f"partial counts must be a contiguous CUDA int32 tensor [{n}, {tiles}, {L}]")
-        return counts, _hip.F_PARTIAL_COUNTS
+            counts = t.empty(shape, dtype=t.int32, device=self.device)
+        elif not (isinstance(counts, t.Tensor) and counts.is_cuda and counts.device == self.device and counts.dtype == t.int32
+                  and tuple(counts.shape) == shape and counts.is_contiguous()):
+            raise ValueError(f"counts must be a contiguous CUDA int32 tensor of shape {shape} on {self.device}")
+        return counts, flag
 
     def svd_detect(self, frames, L, scale=15, want_bits=False, scales=None, blk=4, counts=None, partial=False):
         t = self.torch
@@ -567,18 +571,7 @@ class DctEngine:
         out = self._out(out, frames, (C, n, H, W, 3))
         flag, bits = 0, None
         if L is not None:
-            if partial:
-                tiles = int(self.lib.ofmk_svd_count_tiles(H, W, int(blk)))
-                if tiles < 0:
-                    raise _hip.HipError(f"bad frame size or blk ({H}x{W}, blk={blk})")
-                shape, flag = (C, n, tiles, int(L)), _hip.F_PARTIAL_COUNTS
-            else:
-                shape = (C, n, int(L))
-            if counts is None:
-                counts = t.empty(shape, dtype=t.int32, device=self.device)
-            elif not (isinstance(counts, t.Tensor) and counts.is_cuda and counts.device == self.device and counts.dtype == t.int32
-                      and tuple(counts.shape) == shape and counts.is_contiguous()):
-                raise ValueError(f"counts must be a contiguous CUDA int32 tensor of shape {shape} on {self.device}")
+            counts, flag = self._svd_counts(counts, n, H, W, L, blk, partial, copies=C)
             if want_bits:
                 bits = t.empty((C, n, self.svd_bits_per_frame(H, W, blk)), dtype=t.uint8, device=self.device)
         _hip.check(self.lib.ofmk_svd_embed_copies_rgb8(frames.data_ptr(), out.data_ptr(), C, n, H, W, wm.data_ptr(), wm.shape[0],
@@ -659,18 +652,7 @@ class DctEngine:
         out = self._out(out, planes, (C, n, H * W * 3 // 2))
         flag, bits = 0, None
         if L is not None:
-            if partial:
-                tiles = int(self.lib.ofmk_svd_count_tiles(H, W, int(blk)))
-                if tiles < 0:
-                    raise _hip.HipError(f"bad frame size or blk ({H}x{W}, blk={blk})")
-                shape, flag = (C, n, tiles, int(L)), _hip.F_PARTIAL_COUNTS
-            else:
-                shape = (C, n, int(L))
-            if counts is None:
-                counts = t.empty(shape, dtype=t.int32, device=self.device)
-            elif not (isinstance(counts, t.Tensor) and counts.is_cuda and counts.device == self.device and counts.dtype == t.int32
-                      and tuple(counts.shape) == shape and counts.is_contiguous()):
-                raise ValueError(f"counts must be a contiguous CUDA int32 tensor of shape {shape} on {self.device}")
+            counts, flag = self._svd_counts(counts, n, H, W, L, blk, partial, copies=C)
             if want_bits:
                 bits = t.empty((C, n, self.svd_bits_per_frame(H, W, blk)), dtype=t.uint8, device=self.device)
         _hip.check(self.lib.ofmk_svd_embed_copies_yuv420(planes.data_ptr(), out.data_ptr(), fmt, C, n, H, W, wm.data_ptr(),
