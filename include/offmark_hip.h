@@ -155,6 +155,23 @@ int ofmk_svd_detect_rgb8(const uint8_t *in, int n, int H, int W, int L, const do
 int ofmk_svd_embed_detect_rgb8(const uint8_t *in, uint8_t *out, int n, int H, int W,
                                const uint8_t *wm, int n_wm, const int32_t *wm_row, const double *scales, int blk,
                                int L, int32_t *counts, uint8_t *bits, void *stream, const ofmk_opts *opts);
+/* ---- soft-decision read-out of the DwtDctSvd codec (BUILD EXTENSION, not reference semantics) ---------------------
+ * The reference's decoder thresholds s0 mod scale at scale/2, one bit per unit (an 8x8 pixel block for blk 4, a 16x16 tile for
+ * blk 8); its encoder puts a 0 at (k + 1/4) scale and a 1 at (k + 3/4) scale.  This call keeps the residue: with s0 the top
+ * singular value ofmk_svd_detect_rgb8 forms, r = s0 mod scale (the float32 the hard bit compares with scale/2) and
+ * u = 2 r/scale - 1,
+ *     m = round(sin(pi u) * 2^14) = round(-sin(2 pi s0 / scale) * 2^14)
+ * is -2^14 where a 0 was written, +2^14 where a 1 was, 0 on the thresholds; m > 0 implies ofmk_svd_detect_rgb8's bit is 1 and
+ * m < 0 that it is 0, exactly.
+ *   soft     device int64 [n][L]; soft[f][i] = sum of m over the units c of frame f with c mod L == i -- the convention of
+ *            ofmk_detect_soft_rgb8: positive reads as 1, sums over the frames of a segment may be added before thresholding at
+ *            0 (offmark.dist.vote.soft_vote).  Cleared by the call whatever it held.  scales[1] <= 0: all zeros, as the hard
+ *            read-out.  blk 8 covers the tiles only: fringe pixels contribute nothing.
+ * `scales`, `blk`, L >= 1 and the argument checks (OFMK_E_ARG before any HIP call) as ofmk_svd_detect_rgb8; no partial form:
+ * OFMK_F_PARTIAL_COUNTS is ignored.  Launches are timed as kind 4 (svd).  The reference's hard decision stays the default
+ * everywhere. */
+int ofmk_svd_detect_soft_rgb8(const uint8_t *in, int n, int H, int W, int L, const double *scales, int blk,
+                              long long *soft, void *stream, const ofmk_opts *opts);
 /* ---- C differently marked copies of the same frames in one pass (the A/B workflow) ----------------------------------
  * tests/mark_video_to_hls.py:331-342 decodes every segment once per copy and marks it with payload segment(4b)||copy(4b).
  * These calls read the frames once, do the part of the codec that does not depend on the watermark bit once (DCT: analyze's
@@ -217,6 +234,11 @@ int ofmk_embed_detect_yuv420(const uint8_t *in, uint8_t *out, int layout, int n,
                              const uint8_t *wm, int n_wm, const int32_t *wm_row, double alpha,
                              int L, int32_t *counts, uint8_t *bits,
                              int chunk_frames, void *workspace, size_t workspace_bytes, void *stream, const ofmk_opts *opts);
+/* The DCT codec's soft-decision read-out (BUILD EXTENSION, see ofmk_detect_soft_rgb8) on the same planes: integer for integer,
+ *     ofmk_detect_soft_yuv420 == ofmk_detect_soft_rgb8(ofmk_yuv420_to_rgb8(in)).
+ * Arguments as ofmk_detect_soft_rgb8 plus `layout`; checked as ofmk_detect_yuv420 checks them. */
+int ofmk_detect_soft_yuv420(const uint8_t *in, int layout, int n, int H, int W, int L, double alpha, long long *soft,
+                            int chunk_frames, void *workspace, size_t workspace_bytes, void *stream, const ofmk_opts *opts);
 /* The DwtDctSvd codec on the same 4:2:0 planes.  `scales`, `blk`, `wm` / `n_wm` / `wm_row`, `L` / `counts` / `bits` and `opts`
  * (OFMK_F_PARTIAL_COUNTS included: tiles = ofmk_svd_count_tiles(H, W, blk)) as ofmk_svd_*_rgb8; `layout` and the planes as
  * ofmk_*_yuv420 above; no workspace.  The result is, bit for bit,
@@ -239,6 +261,13 @@ int ofmk_svd_detect_yuv420(const uint8_t *in, int layout, int n, int H, int W, i
 int ofmk_svd_embed_detect_yuv420(const uint8_t *in, uint8_t *out, int layout, int n, int H, int W,
                                  const uint8_t *wm, int n_wm, const int32_t *wm_row, const double *scales, int blk,
                                  int L, int32_t *counts, uint8_t *bits, void *stream, const ofmk_opts *opts);
+/* The DwtDctSvd soft-decision read-out (BUILD EXTENSION, see ofmk_svd_detect_soft_rgb8) on 4:2:0 planes: the same loads and LL
+ * band as ofmk_svd_detect_yuv420, so, integer for integer,
+ *     ofmk_svd_detect_soft_yuv420 == ofmk_svd_detect_soft_rgb8(ofmk_yuv420_to_rgb8(in)).
+ * blk 8 covers the tiles only: fringe pixels contribute nothing.  Arguments are checked as ofmk_svd_detect_yuv420 checks them
+ * (`soft` in place of counts / bits); OFMK_F_PARTIAL_COUNTS is ignored. */
+int ofmk_svd_detect_soft_yuv420(const uint8_t *in, int layout, int n, int H, int W, int L, const double *scales, int blk,
+                                long long *soft, void *stream, const ofmk_opts *opts);
 /* ---- C differently marked copies of the same 4:2:0 frames in one pass: the copies calls above on planes -----------------------
  * The workflow the copies calls serve (tests/mark_video_to_hls.py:331-342) gets its frames from a decoder and hands them to an
  * encoder, so they arrive and leave as 4:2:0 planes.  These calls read the planes once, do what does not depend on the watermark

@@ -7,7 +7,8 @@ labels (.LBB<k>_<i>, .Lfunc_end<k>), and vgpr / sgpr / scratch / LDS from the me
 serial number that runs through the whole listing, so it moves with the order of the kernels too: they are renumbered inside each
 kernel in order of appearance.  For a change that may touch some kernels: every kernel whose text differs is listed with its
 instruction line count in A and in B, and the LDS / global / flat atomic instructions are counted per kernel family (the
-template's name) in A and in B.  Exit status 0 = same set of kernels, all equal."""
+template's name) in A and in B; every kernel that is only in B is listed with its registers / scratch / LDS and the same three atomic
+counts.  Exit status 0 = same set of kernels, all equal."""
 import re
 import sys
 
@@ -53,6 +54,11 @@ for fam in sorted({family(k) for k in both}):
     na, nb = ([sum(len(re.findall(r"^\s*" + op, b[k], re.M)) for k in ks) for op in ("ds_add", "global_atomic", "flat_atomic")] for b in (ba, bb))
     if any(na) or any(nb):
         print(f"  {fam} ({len(ks)}): {na[0]} / {na[1]} / {na[2]} -> {nb[0]} / {nb[1]} / {nb[2]}")
+if only_b:
+    print(f"kernels only in B ({' / '.join(KEYS)}; ds_add / global_atomic / flat_atomic):")
+for k in only_b:
+    n = [len(re.findall(r"^\s*" + op, bb[k], re.M)) for op in ("ds_add", "global_atomic", "flat_atomic")]
+    print(f"  {k}: {' / '.join(map(str, mb[k]))}; {n[0]} / {n[1]} / {n[2]}")
 ok = not (only_a or only_b or text_differs or meta_differs)
 print("SAME DEVICE CODE" if ok else "DEVICE CODE DIFFERS")
 sys.exit(0 if ok else 1)

@@ -173,10 +173,11 @@ void with_fmt(int layout, F &&f) {       // OFMK_YUV_I420 / OFMK_YUV_NV12 -> FMT
     if (layout == OFMK_YUV_I420) f(std::integral_constant<int, FMT_I420>{});
     else f(std::integral_constant<int, FMT_NV12>{});
 }
-// f(mode, multi) of the DwtDctSvd frame kernels; the read-out alone has no MULTI = true form.
+// f(mode, multi) of the DwtDctSvd frame kernels; the read-out alone (hard or soft) has no MULTI = true form.
 template <class F>
 void with_svd_mode(int mode, bool multi, F &&f) {
     if (mode == SVD_DETECT) f(std::integral_constant<int, SVD_DETECT>{}, std::false_type{});
+    else if (mode == SVD_DETECT_SOFT) f(std::integral_constant<int, SVD_DETECT_SOFT>{}, std::false_type{});
     else if (mode == SVD_EMBED) with_bool(multi, [&](auto mu) { f(std::integral_constant<int, SVD_EMBED>{}, mu); });
     else with_bool(multi, [&](auto mu) { f(std::integral_constant<int, SVD_EMBED_VERIFY>{}, mu); });
 }
@@ -253,6 +254,14 @@ int check_detect_args(const void *in, int n, int H, int W, int L, const int32_t 
     if (!in) return fail(OFMK_E_ARG, "null frame pointer%s");
     if (L < 1) return fail(OFMK_E_ARG, "payload length L must be >= 1%s");
     if (!counts && !bits) return fail(OFMK_E_ARG, "both outputs (counts, bits) are null%s");
+    return OFMK_OK;
+}
+
+// the soft read-outs (both codecs): the hard read-out's checks, with the one int64 [n][L] output in place of counts / bits
+int check_soft_args(const void *in, int n, int H, int W, int L, const long long *soft) {
+    if (int rc = check_dims(n, H, W)) return rc;
+    if (!in || !soft) return fail(OFMK_E_ARG, "null pointer%s");
+    if (L < 1) return fail(OFMK_E_ARG, "payload length L must be >= 1%s");
     return OFMK_OK;
 }
 
@@ -671,6 +680,7 @@ struct SvdPlan {
     int bits_per_frame;     // N = H*W/64 (blk 4) or N8 = H*W/256 (blk 8); entries past `units` stay 0
     size_t frame_stride;    // bytes
     int copies;             // outputs per input frame: counts / bits are [copies][n][...]
+    int count_words = 1;    // int32 words per entry of a.counts: 2 for the int64 soft sums of SVD_DETECT_SOFT (SvdArgs::counts)
 };
 struct SvdChunk {
     ScopedTiming timing;    // the KIND_SVD pair of this launch
@@ -685,14 +695,14 @@ template <class Launch>
 int launch_svd(const SvdPlan &p, int n, const SvdArgs &a, const Ctx &cx, Launch &&launch) {
     const size_t count_rows = a.partial ? (size_t)(p.units + kThreads - 1) / kThreads : 1;
     // partial counts: every workgroup stores its own row, nothing to clear (OFMK_F_PARTIAL_COUNTS); else the frames' [L] sums are added into
-    if (a.counts && !a.partial) HIP_TRY(launch_zero(a.counts, (size_t)p.copies * n * a.L * sizeof(int32_t), cx.s));
+    if (a.counts && !a.partial) HIP_TRY(launch_zero(a.counts, (size_t)p.copies * n * a.L * sizeof(int32_t) * p.count_words, cx.s));
     if (a.bits && p.bits_per_frame > p.units) HIP_TRY(launch_zero(a.bits, (size_t)p.copies * n * p.bits_per_frame, cx.s));
     if (p.units == 0) return OFMK_OK;                // frames smaller than a 16x16 tile: no launch, no event pair
     const bool multi = a.scales[0] > 0.f || a.scales[2] > 0.f || !(a.scales[1] > 0.f);      // anything but the default [0, s, 0]
     for_chunks(n, kMaxChunk, [&](int f0, int cf) {
         SvdChunk c{ScopedTiming(KIND_SVD, cx), xcd_grid(p.units, cf), (size_t)f0 * p.frame_stride, f0, cf, multi, a};
         if (c.a.wm_row) c.a.wm_row += f0;
-        if (c.a.counts) c.a.counts += (size_t)f0 * a.L * count_rows;
+        if (c.a.counts) c.a.counts += (size_t)f0 * a.L * count_rows * p.count_words;
         if (c.a.bits) c.a.bits += (size_t)f0 * p.bits_per_frame;
         launch(c);
         return OFMK_OK;
@@ -703,13 +713,15 @@ int launch_svd(const SvdPlan &p, int n, const SvdArgs &a, const Ctx &cx, Launch 
 
 int launch_svd_rgb8(const uint8_t *in, uint8_t *out, int n, int H, int W, int mode, int blk, const SvdArgs &a, const Ctx &cx) {
     int Hc = (H / 8) * 8, Wc = (W / 8) * 8;                // the region the units cover
+    const bool reads = mode == SVD_DETECT || mode == SVD_DETECT_SOFT;      // no frames out
+    const int cw = mode == SVD_DETECT_SOFT ? 2 : 1;
     int rc;
     if (blk == 8) {
         const Geom8 g = make_geom8(H, W);
         const int N8 = (int)((long long)H * W / 256);
         Hc = (((H / 4) * 2) / 8) * 16, Wc = g.wt * 16;
-        const bool al = W % 8 == 0 && (uintptr_t)in % 8 == 0 && (mode == SVD_DETECT || (uintptr_t)out % 8 == 0);
-        rc = launch_svd({g.ntile, N8, g.frame_stride, 1}, n, a, cx, [&](SvdChunk &c) {
+        const bool al = W % 8 == 0 && (uintptr_t)in % 8 == 0 && (reads || (uintptr_t)out % 8 == 0);
+        rc = launch_svd({g.ntile, N8, g.frame_stride, 1, cw}, n, a, cx, [&](SvdChunk &c) {
             Geom8 gc = g;
             gc.frames = c.frames;
             with_bool(al, [&](auto al_) { with_svd_mode(mode, c.multi, [&](auto md, auto mu) {
@@ -719,8 +731,8 @@ int launch_svd_rgb8(const uint8_t *in, uint8_t *out, int n, int H, int W, int mo
         });
     } else {
         const Geom g = svd_geom(H, W);
-        const bool al = aligned_rows(in, W, 1) && (mode == SVD_DETECT || aligned_rows(out, W, 1));
-        rc = launch_svd({g.nblk, a.N, g.frame_stride, 1}, n, a, cx, [&](SvdChunk &c) {
+        const bool al = aligned_rows(in, W, 1) && (reads || aligned_rows(out, W, 1));
+        rc = launch_svd({g.nblk, a.N, g.frame_stride, 1, cw}, n, a, cx, [&](SvdChunk &c) {
             Geom gc = g;
             gc.frames = c.frames;
             with_bool(al, [&](auto al_) { with_svd_mode(mode, c.multi, [&](auto md, auto mu) {
@@ -730,7 +742,7 @@ int launch_svd_rgb8(const uint8_t *in, uint8_t *out, int n, int H, int W, int mo
         });
     }
     if (rc) return rc;
-    if (mode != SVD_DETECT && in != out && (Hc != H || Wc != W)) {
+    if (!reads && in != out && (Hc != H || Wc != W)) {
         launch_copy_fringe(in, out, n, H, W, Hc, Wc, cx.s);
         HIP_TRY(hipGetLastError());
     }
@@ -742,8 +754,9 @@ int launch_svd_rgb8(const uint8_t *in, uint8_t *out, int n, int H, int W, int mo
 // launch (also timed under KIND_SVD) -- also in place, where the RGB path has nothing to copy.
 int launch_svd_yuv420(const uint8_t *in, uint8_t *out, int layout, int n, int H, int W, int mode, int blk, const SvdArgs &a, const Ctx &cx) {
     const PGeom g = make_pgeom(layout, H, W, 0);
+    const int cw = mode == SVD_DETECT_SOFT ? 2 : 1;
     if (blk == 4)
-        return launch_svd({g.nblk, a.N, g.frame_stride, 1}, n, a, cx, [&](SvdChunk &c) {
+        return launch_svd({g.nblk, a.N, g.frame_stride, 1, cw}, n, a, cx, [&](SvdChunk &c) {
             with_fmt(layout, [&](auto fmt) { with_svd_mode(mode, c.multi, [&](auto md, auto mu) {
                 OFMK_TIMED_LAUNCH(c.timing, (svd_yuv420_kernel<decltype(fmt)::value, decltype(md)::value, decltype(mu)::value>), c.grid, dim3(kThreads), 0, cx.s,
                                   in + c.offset, out ? out + c.offset : nullptr, g, c.frames, c.a);
@@ -751,7 +764,7 @@ int launch_svd_yuv420(const uint8_t *in, uint8_t *out, int layout, int n, int H,
         });
     const Geom8 g8 = make_geom8(H, W);
     const int N8 = (int)((long long)H * W / 256);
-    int rc = launch_svd({g8.ntile, N8, g.frame_stride, 1}, n, a, cx, [&](SvdChunk &c) {
+    int rc = launch_svd({g8.ntile, N8, g.frame_stride, 1, cw}, n, a, cx, [&](SvdChunk &c) {
         Geom8 gc = g8;
         gc.frames = c.frames;
         with_fmt(layout, [&](auto fmt) { with_svd_mode(mode, c.multi, [&](auto md, auto mu) {
@@ -762,7 +775,7 @@ int launch_svd_yuv420(const uint8_t *in, uint8_t *out, int layout, int n, int H,
     if (rc) return rc;
     const int hcb = (((H / 4) * 2) / 8) * 2, wcb = g8.wt * 2;                 // the tiles' Hc x Wc region in 8x8 pixel blocks
     const int nfringe = g.nblk - hcb * wcb;
-    if (mode == SVD_DETECT || nfringe <= 0) return OFMK_OK;
+    if (mode == SVD_DETECT || mode == SVD_DETECT_SOFT || nfringe <= 0) return OFMK_OK;
     for_chunks(n, kMaxChunk, [&](int f0, int cf) {
         const size_t fo = (size_t)f0 * g.frame_stride;
         ScopedTiming timing(KIND_SVD, cx);
@@ -772,6 +785,18 @@ int launch_svd_yuv420(const uint8_t *in, uint8_t *out, int layout, int n, int H,
         return OFMK_OK;
     });
     HIP_TRY(hipGetLastError());
+    return OFMK_OK;
+}
+
+// The DwtDctSvd soft read-out behind ofmk_svd_detect_soft_*: the int64 [n][L] sums travel in SvdArgs::counts; OFMK_F_PARTIAL_COUNTS
+// is not looked at (the soft sums have no partial form); scales[1] <= 0: all zeros, as the hard read-out.  launch(a) is the
+// variant's launcher in SVD_DETECT_SOFT mode.
+template <class Launch>
+int svd_detect_soft(int n, int H, int W, int L, const double *scales, long long *soft, void *stream, Launch &&launch) {
+    SvdArgs a;
+    if (int rc = make_svd_args(a, H, W, scales, true, nullptr, 0, nullptr, L, reinterpret_cast<int32_t *>(soft), nullptr, nullptr)) return rc;
+    if (a.scales[1] > 0.f) return launch(a);
+    HIP_TRY(launch_zero(soft, (size_t)n * L * sizeof(long long), static_cast<hipStream_t>(stream)));
     return OFMK_OK;
 }
 
@@ -904,10 +929,8 @@ int ofmk_detect_rgb8(const uint8_t *in, int n, int H, int W, int L, double alpha
 int ofmk_detect_soft_rgb8(const uint8_t *in, int n, int H, int W, int L, double alpha, long long *soft, int chunk_frames,
                           void *workspace, size_t workspace_bytes, void *stream, const ofmk_opts *opts) {
     if (int orc = check_opts(opts)) return orc;
-    int rc = check_dims(n, H, W);
+    int rc = check_soft_args(in, n, H, W, L, soft);
     if (rc) return rc;
-    if (!in || !soft) return fail(OFMK_E_ARG, "null pointer%s");
-    if (L < 1) return fail(OFMK_E_ARG, "payload length L must be >= 1%s");
     Workspace ws;
     if ((rc = carve(workspace, workspace_bytes, H, W, chunk_frames, ws))) return rc;
     const Ctx cx = make_ctx(stream, opts);
@@ -1034,6 +1057,19 @@ int ofmk_svd_detect_rgb8(const uint8_t *in, int n, int H, int W, int L, const do
     if ((rc = make_svd_args(a, H, W, scales, true, nullptr, 0, nullptr, L, counts, bits, opts))) return rc;
     if (!(a.scales[1] > 0.f)) return zero_svd_readout(n, H, W, blk, a, static_cast<hipStream_t>(stream));
     return launch_svd_rgb8(in, nullptr, n, H, W, SVD_DETECT, blk, a, make_ctx(stream, opts));
+}
+
+// Build extension, not reference semantics: per payload position the sum over the frame's units of svd_soft_metric
+// (svd_kernels.hiph), int64 [n][L], cleared here whatever it held.  scales[1] <= 0: all zeros, as the hard read-out.
+int ofmk_svd_detect_soft_rgb8(const uint8_t *in, int n, int H, int W, int L, const double *scales, int blk, long long *soft,
+                              void *stream, const ofmk_opts *opts) {
+    if (int orc = check_opts(opts)) return orc;
+    int rc = check_soft_args(in, n, H, W, L, soft);
+    if (rc) return rc;
+    if ((rc = check_blk(blk))) return rc;
+    return svd_detect_soft(n, H, W, L, scales, soft, stream, [&](const SvdArgs &a) {
+        return launch_svd_rgb8(in, nullptr, n, H, W, SVD_DETECT_SOFT, blk, a, make_ctx(stream, opts));
+    });
 }
 
 int ofmk_svd_embed_detect_rgb8(const uint8_t *in, uint8_t *out, int n, int H, int W, const uint8_t *wm, int n_wm,
@@ -1194,6 +1230,27 @@ int ofmk_detect_yuv420(const uint8_t *in, int layout, int n, int H, int W, int L
     return for_chunks(n, ws.frames, [&](int f0, int cf) { return detect_chunk_yuv420(in, layout, f0, cf, H, W, L, alpha, counts, bits, ws, cx); });
 }
 
+// The DCT codec's soft metric (ofmk_detect_soft_rgb8) for planar callers: the planar analysis, then the same finalize.
+int ofmk_detect_soft_yuv420(const uint8_t *in, int layout, int n, int H, int W, int L, double alpha, long long *soft, int chunk_frames,
+                            void *workspace, size_t workspace_bytes, void *stream, const ofmk_opts *opts) {
+    if (int orc = check_opts(opts)) return orc;
+    int rc = check_soft_args(in, n, H, W, L, soft);
+    if (rc) return rc;
+    if ((rc = check_planar(layout, H, W, in, nullptr))) return rc;
+    Workspace ws;
+    if ((rc = carve(workspace, workspace_bytes, H, W, chunk_frames, ws))) return rc;
+    const Ctx cx = make_ctx(stream, opts);
+    HIP_TRY(launch_zero(soft, (size_t)n * L * sizeof(long long), cx.s));
+    const size_t fs = (size_t)H * W * 3 / 2;
+    return for_chunks(n, ws.frames, [&](int f0, int cf) {
+        if (int rc = launch_analyze_yuv420(in + (size_t)f0 * fs, layout, cf, H, W, ws, cx)) return rc;
+        FinArgs a = fin_base(ws, H, W, alpha);
+        a.L = L;
+        a.soft = soft + (size_t)f0 * L;
+        return launch_finalize(a, cf, cx);
+    });
+}
+
 int ofmk_embed_detect_yuv420(const uint8_t *in, uint8_t *out, int layout, int n, int H, int W, const uint8_t *wm, int n_wm,
                              const int32_t *wm_row, double alpha, int L, int32_t *counts, uint8_t *bits, int chunk_frames,
                              void *workspace, size_t workspace_bytes, void *stream, const ofmk_opts *opts) {
@@ -1240,6 +1297,19 @@ int ofmk_svd_detect_yuv420(const uint8_t *in, int layout, int n, int H, int W, i
     if ((rc = make_svd_args(a, H, W, scales, true, nullptr, 0, nullptr, L, counts, bits, opts))) return rc;
     if (!(a.scales[1] > 0.f)) return zero_svd_readout(n, H, W, blk, a, static_cast<hipStream_t>(stream));
     return launch_svd_yuv420(in, nullptr, layout, n, H, W, SVD_DETECT, blk, a, make_ctx(stream, opts));
+}
+
+// == ofmk_svd_detect_soft_rgb8(ofmk_yuv420_to_rgb8(in)), integer for integer (the same loads and LL band as the hard read-out)
+int ofmk_svd_detect_soft_yuv420(const uint8_t *in, int layout, int n, int H, int W, int L, const double *scales, int blk,
+                                long long *soft, void *stream, const ofmk_opts *opts) {
+    if (int orc = check_opts(opts)) return orc;
+    int rc = check_soft_args(in, n, H, W, L, soft);
+    if (rc) return rc;
+    if ((rc = check_blk(blk))) return rc;
+    if ((rc = check_planar(layout, H, W, in, nullptr))) return rc;
+    return svd_detect_soft(n, H, W, L, scales, soft, stream, [&](const SvdArgs &a) {
+        return launch_svd_yuv420(in, nullptr, layout, n, H, W, SVD_DETECT_SOFT, blk, a, make_ctx(stream, opts));
+    });
 }
 
 int ofmk_svd_embed_detect_yuv420(const uint8_t *in, uint8_t *out, int layout, int n, int H, int W, const uint8_t *wm, int n_wm,

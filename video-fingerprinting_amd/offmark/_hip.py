@@ -52,6 +52,7 @@ SIGNATURES = {
     "ofmk_stage_mark_rgb8": (_i32, [_vp, _vp, _i32, _i32, _i32, _vp, _f64, _i32, _vp, _sz, _vp, _op]),
     "ofmk_svd_embed_rgb8": (_i32, [_vp, _vp, _i32, _i32, _i32, _vp, _i32, _vp, _dp, _i32, _vp, _op]),
     "ofmk_svd_detect_rgb8": (_i32, [_vp, _i32, _i32, _i32, _i32, _dp, _i32, _vp, _vp, _vp, _op]),
+    "ofmk_svd_detect_soft_rgb8": (_i32, [_vp, _i32, _i32, _i32, _i32, _dp, _i32, _vp, _vp, _op]),
     "ofmk_svd_embed_detect_rgb8": (_i32, [_vp, _vp, _i32, _i32, _i32, _vp, _i32, _vp, _dp, _i32, _i32, _vp, _vp, _vp, _op]),
     "ofmk_embed_copies_rgb8": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _f64, _i32, _vp, _sz, _vp, _op]),
     "ofmk_svd_embed_copies_rgb8": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _dp, _i32, _i32, _vp, _vp, _vp,
@@ -63,10 +64,12 @@ SIGNATURES = {
     "ofmk_payloads_from_partial_counts": (_i32, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _op]),
     "ofmk_embed_yuv420": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _f64, _i32, _vp, _sz, _vp, _op]),
     "ofmk_detect_yuv420": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _f64, _vp, _vp, _i32, _vp, _sz, _vp, _op]),
+    "ofmk_detect_soft_yuv420": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _f64, _vp, _i32, _vp, _sz, _vp, _op]),
     "ofmk_embed_detect_yuv420": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _f64, _i32, _vp, _vp, _i32, _vp,
                                         _sz, _vp, _op]),
     "ofmk_svd_embed_yuv420": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _dp, _i32, _vp, _op]),
     "ofmk_svd_detect_yuv420": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _dp, _i32, _vp, _vp, _vp, _op]),
+    "ofmk_svd_detect_soft_yuv420": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _dp, _i32, _vp, _vp, _op]),
     "ofmk_svd_embed_detect_yuv420": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _dp, _i32, _i32, _vp, _vp, _vp,
                                             _op]),
     "ofmk_embed_copies_yuv420": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _f64, _i32, _vp, _sz, _vp, _op]),

@@ -219,6 +219,16 @@ class DctEngine:
             raise ValueError(f"counts must be a contiguous CUDA int32 tensor of shape {(n, L)} on {self.device}")
         return counts
 
+    def _soft(self, soft, n, L):
+        """The soft sums of a call: a fresh int64 [n, L] tensor, or the caller's (whatever it holds: the library clears it)."""
+        t = self.torch
+        if soft is None:
+            return t.empty((n, L), dtype=t.int64, device=self.device)
+        if not (isinstance(soft, t.Tensor) and soft.is_cuda and soft.device == self.device and soft.dtype == t.int64
+                and tuple(soft.shape) == (n, L) and soft.is_contiguous()):
+            raise ValueError(f"soft must be a contiguous CUDA int64 tensor of shape {(n, L)} on {self.device}")
+        return soft
+
     def _layout(self, layout):
         try:
             return self._LAYOUT[layout]
@@ -288,11 +298,11 @@ class DctEngine:
                                              self._o()))
         return counts, bits
 
-    def detect_soft(self, frames, L, alpha=20):
+    def detect_soft(self, frames, L, alpha=20, soft=None):
         """Build extension (not reference semantics): per-position soft sums, int64 [n, L]; > 0 reads as 1."""
         t = self.torch
         n, H, W = self._check_frames(frames, t.uint8)
-        soft = t.empty((n, L), dtype=t.int64, device=self.device)
+        soft = self._soft(soft, n, L)
         cf = self._chunk(n, H, W)
         ws = self.workspace(H, W, cf)
         _hip.check(self.lib.ofmk_detect_soft_rgb8(frames.data_ptr(), n, H, W, int(L), float(alpha), soft.data_ptr(), cf,
@@ -390,6 +400,17 @@ class DctEngine:
                                                counts.data_ptr(), _hip.ptr(bits), cf, ws.data_ptr(), ws.numel(),
                                                _hip.current_stream(), self._o()))
         return counts, bits
+
+    def detect_soft_yuv420(self, planes, H, W, L, alpha=20, layout="i420", soft=None):
+        """Build extension (not reference semantics): detect_soft on 4:2:0 planes, int64 [n, L]; equal, integer for integer,
+        to detect_soft(yuv420_to_rgb(planes))."""
+        n = self._check_planar(planes, H, W)
+        soft = self._soft(soft, n, L)
+        cf = self._chunk(n, H, W)
+        ws = self.workspace(H, W, cf)
+        _hip.check(self.lib.ofmk_detect_soft_yuv420(planes.data_ptr(), self._layout(layout), n, H, W, int(L), float(alpha),
+                                                    soft.data_ptr(), cf, ws.data_ptr(), ws.numel(), _hip.current_stream(), self._o()))
+        return soft
 
     def embed_detect_yuv420(self, planes, H, W, wm, L, alpha=20, wm_row=None, out=None, want_bits=False, layout="i420", counts=None):
         """Mark and verify on planes; counts/bits are what a reader of the WRITTEN planes gets."""
@@ -496,6 +517,17 @@ class DctEngine:
         _hip.check(self.lib.ofmk_svd_detect_rgb8(frames.data_ptr(), n, H, W, int(L), _hip.scales3(scale, scales), int(blk), counts.data_ptr(),
                                                  _hip.ptr(bits), _hip.current_stream(), self._o(extra_flags=flag)))
         return counts, bits
+
+    def svd_detect_soft(self, frames, L, scale=15, scales=None, blk=4, soft=None):
+        """Build extension (not reference semantics): the DwtDctSvd read-out's soft sums, int64 [n, L].  Per unit (8x8 pixel
+        block for blk 4, 16x16 tile for blk 8) round(-sin(2 pi s0 / scale) * 2^14), summed over the units c with c % L == i:
+        > 0 reads as 1, the sign agrees with svd_detect's bit, sums over frames may be added (dist.vote.soft_vote)."""
+        t = self.torch
+        n, H, W = self._check_frames(frames, t.uint8)
+        soft = self._soft(soft, n, L)
+        _hip.check(self.lib.ofmk_svd_detect_soft_rgb8(frames.data_ptr(), n, H, W, int(L), _hip.scales3(scale, scales), int(blk),
+                                                      soft.data_ptr(), _hip.current_stream(), self._o()))
+        return soft
 
     def svd_embed_detect(self, frames, wm, L, scale=15, wm_row=None, out=None, want_bits=False, scales=None, blk=4, counts=None,
                          partial=False):
@@ -604,6 +636,16 @@ class DctEngine:
                                                    int(blk), counts.data_ptr(), _hip.ptr(bits), _hip.current_stream(),
                                                    self._o(extra_flags=flag)))
         return counts, bits
+
+    def svd_detect_soft_yuv420(self, planes, H, W, L, scale=15, scales=None, blk=4, layout="i420", soft=None):
+        """Build extension (not reference semantics): svd_detect_soft on 4:2:0 planes, int64 [n, L]; equal, integer for integer,
+        to svd_detect_soft(yuv420_to_rgb(planes))."""
+        n = self._check_planar(planes, H, W)
+        soft = self._soft(soft, n, L)
+        _hip.check(self.lib.ofmk_svd_detect_soft_yuv420(planes.data_ptr(), self._layout(layout), n, H, W, int(L),
+                                                        _hip.scales3(scale, scales), int(blk), soft.data_ptr(), _hip.current_stream(),
+                                                        self._o()))
+        return soft
 
     def svd_embed_detect_yuv420(self, planes, H, W, wm, L, scale=15, wm_row=None, out=None, want_bits=False, scales=None, blk=4,
                                 counts=None, partial=False, layout="i420"):

@@ -51,3 +51,12 @@ class DctDecoder:
     def decode_planes_yuv420(self, planes, height, width, payload_len, want_bits=False, layout="i420"):
         """planes: CUDA uint8 [n, 1.5*H*W] (I420 or NV12) -> (counts int32 [n, L] on device, bits or None)."""
         return self.engine.detect_yuv420(planes, height, width, payload_len, alpha=self.alpha, want_bits=want_bits, layout=layout)
+
+    # -- soft read-out (build extension, not reference semantics: engine.detect_soft) -------------------------------------
+    def decode_soft_frames_u8(self, frames, payload_len):
+        """frames: CUDA uint8 [n, H, W, 3] -> soft sums int64 [n, L] on device (> 0 reads as 1)."""
+        return self.engine.detect_soft(frames, payload_len, alpha=self.alpha)
+
+    def decode_soft_planes_yuv420(self, planes, height, width, payload_len, layout="i420"):
+        """planes: CUDA uint8 [n, 1.5*H*W] (I420 or NV12) -> soft sums int64 [n, L] on device."""
+        return self.engine.detect_soft_yuv420(planes, height, width, payload_len, alpha=self.alpha, layout=layout)

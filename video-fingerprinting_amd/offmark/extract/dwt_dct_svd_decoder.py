@@ -44,3 +44,12 @@ class DwtDctSvdDecoder:
         """planes: CUDA uint8 [n, 1.5*H*W] (I420 or NV12) -> (counts int32 [n, L] on device, bits or None)."""
         return self.engine.svd_detect_yuv420(planes, height, width, payload_len, scales=self._scales, want_bits=want_bits,
                                              blk=self.blk, layout=layout)
+
+    # -- soft read-out (build extension, not reference semantics: engine.svd_detect_soft) ---------------------------------
+    def decode_soft_frames_u8(self, frames, payload_len):
+        """frames: CUDA uint8 [n, H, W, 3] -> soft sums int64 [n, L] on device (> 0 reads as 1)."""
+        return self.engine.svd_detect_soft(frames, payload_len, scales=self._scales, blk=self.blk)
+
+    def decode_soft_planes_yuv420(self, planes, height, width, payload_len, layout="i420"):
+        """planes: CUDA uint8 [n, 1.5*H*W] (I420 or NV12) -> soft sums int64 [n, L] on device."""
+        return self.engine.svd_detect_soft_yuv420(planes, height, width, payload_len, scales=self._scales, blk=self.blk, layout=layout)
