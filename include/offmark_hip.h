@@ -202,6 +202,33 @@ int ofmk_embed_copies_rgb8(const uint8_t *in, uint8_t *out, int copies, int n, i
 int ofmk_svd_embed_copies_rgb8(const uint8_t *in, uint8_t *out, int copies, int n, int H, int W,
                                const uint8_t *wm, int n_wm, const int32_t *wm_rows, const double *scales, int blk,
                                int L, int32_t *counts, uint8_t *bits, void *stream, const ofmk_opts *opts);
+/* ---- the DCT codec's copies with the verify of every copy in the same pass -----------------------------------------------------
+ * tests/mark_video_to_hls.py:356-389 verifies every marked copy.  ofmk_embed_detect_copies_rgb8 is ofmk_embed_copies_rgb8 plus the
+ * read-out of every copy from the pixels the mark kernel still holds (as ofmk_embed_detect_rgb8 does for one copy): per chunk one
+ * analysis of the input, one fused launch that writes every copy and every copy's block records, and the finalize of each copy's
+ * records (one small launch per copy) -- 6 + 3 * copies bytes per pixel instead of 6 + 6 * copies for ofmk_embed_copies_rgb8
+ * followed by ofmk_detect_rgb8 of each copy.
+ *   out      device u8 [copies][n][H][W][3]: byte for byte what ofmk_embed_copies_rgb8 writes, fringe pixels included
+ *   counts   device int32 [copies][n][L], bits device u8 [copies][n][N] (N = H*W/64; entries past (H/8)*(W/8) are 0); either may be
+ *            NULL, not both.  For copy c they are what ofmk_embed_detect_rgb8(in, ..., wm_rows + c*n, ...) returns -- by that
+ *            function's contract ofmk_detect_rgb8 of out[c] -- integer for integer.  They may hold anything before the call: the
+ *            fused kernel clears the sums finalize adds into (no fill dispatch).
+ *   workspace  every copy's marked frame has its own frame mean, so every copy has its own records next to the input's:
+ *            ofmk_copies_workspace_bytes(frames_in_flight, copies, H, W) bytes (0 on bad arguments; monotone in frames_in_flight
+ *            and in copies; >= ofmk_workspace_bytes(frames_in_flight, H, W)).  Any workspace >= ofmk_copies_workspace_bytes(1,
+ *            copies, H, W) is accepted and the call sizes its chunks to what fits; a smaller one: OFMK_E_WORKSPACE.
+ *   OFMK_F_SEPARATE_DETECT runs the literal sequence instead -- the non-fused copies mark, then analyze + finalize of each written
+ *   copy -- with the same results.  Tile-order flags as ofmk_embed_copies_rgb8.  Launches are timed as kind 3 (the fused launch), 0
+ *   (analyze) and 1 (finalize); the separate route's mark as kind 2.
+ *   With copies == 1 the call equals ofmk_embed_detect_rgb8; no result depends on chunk_frames, the workspace size or the tile
+ *   order.  Arguments are checked before any HIP call (OFMK_E_ARG): as ofmk_embed_copies_rgb8, plus L >= 1 and a non-NULL counts
+ *   or bits as ofmk_embed_detect_rgb8.  The call only enqueues (no allocation, no synchronisation), so it captures into a hipGraph. */
+size_t ofmk_copies_workspace_bytes(int frames_in_flight, int copies, int H, int W);
+int ofmk_embed_detect_copies_rgb8(const uint8_t *in, uint8_t *out, int copies, int n, int H, int W,
+                                  const uint8_t *wm, int n_wm, const int32_t *wm_rows, double alpha,
+                                  int L, int32_t *counts, uint8_t *bits,
+                                  int chunk_frames, void *workspace, size_t workspace_bytes, void *stream,
+                                  const ofmk_opts *opts);
 /* plugin level, float32 YUV [n][H][W][3] (n <= 65535): encode mutates the marked channels; decode fills bits */
 int ofmk_svd_encode_yuv32f(float *yuv, int n, int H, int W,
                            const uint8_t *wm, int n_wm, const int32_t *wm_row, const double *scales, int blk, void *stream,

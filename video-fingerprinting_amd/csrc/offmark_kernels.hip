@@ -458,8 +458,8 @@ int detect_chunk(const void *in, int src, int f0, int cf, int H, int W, int L, d
 }
 
 // The copies half of a copies kernel's arguments, for a launch that starts at frame f0 of the call's n: wm_rows is the call's
-// [copies][n] table or null, out the call's [copies][n] frames of frame_bytes.  DwtDctSvd verify: a copy's counts are
-// counts_per_frame int32 entries per frame (the DCT codec's copies have no read-out: 0), its bits bits_per_frame bytes.
+// [copies][n] table or null, out the call's [copies][n] frames of frame_bytes.  Verify: a copy's counts are counts_per_frame
+// int32 entries per frame (0 for the DCT codec's copies without a read-out), its bits bits_per_frame bytes.
 CopyArgs make_copy_args(int copies, int n, int f0, const int32_t *wm_rows, size_t frame_bytes, size_t counts_per_frame = 0,
                         size_t bits_per_frame = 0) {
     CopyArgs k;
@@ -490,6 +490,83 @@ int launch_mark_copies_rgb8(const uint8_t *in, uint8_t *out, int copies, int n, 
     });
     HIP_TRY(hipGetLastError());
     return OFMK_OK;
+}
+
+// ---- the DCT codec's copies with verify (copies_kernels.hiph: mark_verify_copies_rgb8_kernel) ------------------------------
+// The workspace of ofmk_embed_detect_copies_rgb8: the single-copy calls' arrays for the chunk's frames, and behind them every
+// copy's own records and per-tile sums of the frames it was marked into.
+struct CopiesWorkspace {
+    Workspace base;               // the input frames' records (analyze); the separate route's detect of a copy reuses it
+    float *rec;                   // kRec planes of [copies][frames][nblk]
+    unsigned long long *ysum;     // [copies][frames][tiles]
+    size_t plane;                 // copies * frames * nblk
+};
+
+size_t per_frame_copies_bytes(int copies, int H, int W) {
+    const size_t nblk = (size_t)(H / 8) * (W / 8);
+    return per_frame_bytes(H, W) + (size_t)copies * (nblk * kRec * sizeof(float) + tiles_per_frame(H, W) * 8);
+}
+
+int carve_copies(void *ws, size_t bytes, int copies, int H, int W, int want_frames, CopiesWorkspace &out) {
+    if (!ws) return fail(OFMK_E_ARG, "workspace is null%s");
+    if ((uintptr_t)ws % 256) return fail(OFMK_E_ARG, "workspace must be 256-byte aligned%s");
+    const size_t per = per_frame_copies_bytes(copies, H, W);
+    if (bytes < per + kFixedBytes) return fail(OFMK_E_WORKSPACE, "workspace smaller than ofmk_copies_workspace_bytes(1, copies, H, W)%s");
+    size_t cap = (bytes - kFixedBytes) / per;
+    if (want_frames > 0 && (size_t)want_frames < cap) cap = want_frames;
+    if (cap > (size_t)kMaxChunk) cap = kMaxChunk;
+    // the front of the buffer is the single-copy layout for `cap` frames (carve clamps to the same cap: it sees more bytes per frame)
+    if (int rc = carve(ws, bytes, H, W, (int)cap, out.base)) return rc;
+    const size_t nblk = (size_t)(H / 8) * (W / 8);
+    char *p = reinterpret_cast<char *>(out.base.ysum2) + align256(cap * out.base.tiles * 8);
+    out.plane = (size_t)copies * cap * nblk;
+    out.rec = reinterpret_cast<float *>(p);
+    p += align256(out.plane * kRec * sizeof(float));
+    out.ysum = reinterpret_cast<unsigned long long *>(p);
+    return OFMK_OK;
+}
+
+// One chunk of frames [f0, f0+cf) after launch_analyze left their records in ws.base: every copy of them, and every copy's
+// records, in one launch; zero_counts (the call's counts, or null) is cleared for these frames in every copy.
+int launch_mark_verify_copies_rgb8(const uint8_t *in, uint8_t *out, int copies, int n, int f0, int cf, int H, int W, const uint8_t *wm,
+                                   int n_wm, const int32_t *wm_rows, double alpha, int L, int32_t *zero_counts,
+                                   const CopiesWorkspace &ws, const Ctx &cx) {
+    const size_t fs = (size_t)H * W * 3;
+    const uint8_t *pin = in + (size_t)f0 * fs;
+    uint8_t *pout = out + (size_t)f0 * fs;
+    const int xc = tile_xcds(cx, (size_t)cf * fs);
+    const Geom g = make_geom(H, W, ws.base, cf, xc);
+    const dim3 grid = xcd_grid(g.nblk, cf, xc);
+    const MarkArgs m = mark_args(ws.base, H, W, wm, n_wm, nullptr, alpha);
+    const CopyArgs k = make_copy_args(copies, n, f0, wm_rows, fs, (size_t)L, (size_t)m.N);
+    CopyRecs v;
+    v.rec = ws.rec;
+    v.ysum = ws.ysum;
+    v.plane = ws.plane;
+    v.rec_stride = (size_t)ws.base.frames * g.nblk;
+    v.ysum_stride = (size_t)ws.base.frames * ws.base.tiles;
+    v.zero_counts = zero_counts ? zero_counts + (size_t)f0 * L : nullptr;
+    v.L = L;
+    ScopedTiming timing(KIND_MARK_FUSED, cx);
+    with_bool(aligned_rows(in, W, 1) && aligned_rows(out, W, 1), [&](auto al) {     // frame and copy strides are multiples of 8 when W is
+        OFMK_TIMED_LAUNCH(timing, mark_verify_copies_rgb8_kernel<decltype(al)::value>, grid, dim3(kThreads), 0, cx.s, pin, pout, g, m, k, v);
+    });
+    HIP_TRY(hipGetLastError());
+    return OFMK_OK;
+}
+
+// The read-out of copy q's records of frames [f0, f0+cf), left by launch_mark_verify_copies_rgb8: counts / bits are the call's
+// [copies][n][...] arrays.
+int finalize_detect_copy(int q, int n, int f0, int cf, int H, int W, int L, double alpha, int32_t *counts, uint8_t *bits,
+                         const CopiesWorkspace &ws, const Ctx &cx) {
+    FinArgs a = fin_base(ws.base, H, W, alpha);
+    a.rec = ws.rec + (size_t)q * ws.base.frames * a.nblk;
+    a.plane = ws.plane;
+    a.ysum = ws.ysum + (size_t)q * ws.base.frames * ws.base.tiles;
+    a.L = L;
+    a.counts = counts ? counts + ((size_t)q * n + f0) * L : nullptr;
+    a.bits = bits ? bits + ((size_t)q * n + f0) * a.N : nullptr;
+    return launch_finalize(a, cf, cx);
 }
 
 // ---- planar YUV 4:2:0 (I420 / NV12) -------------------------------------------------------------
@@ -1098,6 +1175,44 @@ int ofmk_embed_copies_rgb8(const uint8_t *in, uint8_t *out, int copies, int n, i
     rc = for_chunks(n, ws.frames, [&](int f0, int cf) {      // one analysis per chunk serves every copy
         if (int rc = launch_analyze(in + (size_t)f0 * H * W * 3, SRC_RGB8, cf, H, W, ws, cx)) return rc;
         return launch_mark_copies_rgb8(in, out, copies, n, f0, cf, H, W, wm, n_wm, wm_rows, alpha, ws, cx);
+    });
+    if (rc) return rc;
+    return launch_copy_fringe_copies(in, out, copies, n, H, W, cx.s);
+}
+
+size_t ofmk_copies_workspace_bytes(int frames_in_flight, int copies, int H, int W) {
+    if (frames_in_flight < 1 || copies < 1 || copies > kMaxCopies || H < 8 || W < 8) return 0;
+    return per_frame_copies_bytes(copies, H, W) * (size_t)frames_in_flight + kFixedBytes;
+}
+
+int ofmk_embed_detect_copies_rgb8(const uint8_t *in, uint8_t *out, int copies, int n, int H, int W, const uint8_t *wm, int n_wm,
+                                  const int32_t *wm_rows, double alpha, int L, int32_t *counts, uint8_t *bits, int chunk_frames,
+                                  void *workspace, size_t workspace_bytes, void *stream, const ofmk_opts *opts) {
+    if (int orc = check_opts(opts)) return orc;
+    int rc = check_embed_args(in, out, n, H, W, wm, n_wm);
+    if (rc) return rc;
+    if ((rc = check_copies(in, out, copies, n, (size_t)H * W * 3))) return rc;
+    if ((rc = check_detect_args(out, n, H, W, L, counts, bits))) return rc;
+    CopiesWorkspace ws;
+    if ((rc = carve_copies(workspace, workspace_bytes, copies, H, W, chunk_frames, ws))) return rc;
+    const Ctx cx = make_ctx(stream, opts);
+    const size_t fs = (size_t)H * W * 3;
+    const size_t N = (size_t)((long long)H * W / 64);
+    rc = for_chunks(n, ws.base.frames, [&](int f0, int cf) {      // one analysis of the input per chunk serves every copy
+        if (int rc = launch_analyze(in + (size_t)f0 * fs, SRC_RGB8, cf, H, W, ws.base, cx)) return rc;
+        if (!(cx.flags & OFMK_F_SEPARATE_DETECT)) {
+            if (int rc = launch_mark_verify_copies_rgb8(in, out, copies, n, f0, cf, H, W, wm, n_wm, wm_rows, alpha, L, counts, ws, cx)) return rc;
+            for (int q = 0; q < copies; ++q)
+                if (int rc = finalize_detect_copy(q, n, f0, cf, H, W, L, alpha, counts, bits, ws, cx)) return rc;
+            return (int)OFMK_OK;
+        }
+        // the literal sequence: mark every copy, then detect each written copy (its analysis overwrites the input's records,
+        // which the chunk's mark launch, earlier in the stream, has already used)
+        if (int rc = launch_mark_copies_rgb8(in, out, copies, n, f0, cf, H, W, wm, n_wm, wm_rows, alpha, ws.base, cx)) return rc;
+        for (int q = 0; q < copies; ++q)
+            if (int rc = detect_chunk(out + (size_t)q * n * fs, SRC_RGB8, f0, cf, H, W, L, alpha, counts ? counts + (size_t)q * n * L : nullptr,
+                                      bits ? bits + (size_t)q * n * N : nullptr, ws.base, cx)) return rc;
+        return (int)OFMK_OK;
     });
     if (rc) return rc;
     return launch_copy_fringe_copies(in, out, copies, n, H, W, cx.s);

@@ -57,6 +57,9 @@ SIGNATURES = {
     "ofmk_embed_copies_rgb8": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _f64, _i32, _vp, _sz, _vp, _op]),
     "ofmk_svd_embed_copies_rgb8": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _dp, _i32, _i32, _vp, _vp, _vp,
                                           _op]),
+    "ofmk_copies_workspace_bytes": (_sz, [_i32, _i32, _i32, _i32]),
+    "ofmk_embed_detect_copies_rgb8": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _f64, _i32, _vp, _vp, _i32, _vp, _sz,
+                                             _vp, _op]),
     "ofmk_svd_encode_yuv32f": (_i32, [_vp, _i32, _i32, _i32, _vp, _i32, _vp, _dp, _i32, _vp, _op]),
     "ofmk_svd_decode_yuv32f": (_i32, [_vp, _i32, _i32, _i32, _dp, _i32, _vp, _vp, _op]),
     "ofmk_payloads_from_counts": (_i32, [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _op]),

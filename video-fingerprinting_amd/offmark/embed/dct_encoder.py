@@ -82,11 +82,16 @@ class DctEncoder:
         wm = wm_table if wm_table is not None else self._device_wm(h * w // 64)
         return self.engine.embed(frames, wm, alpha=self.alpha, wm_row=wm_rows, out=out)
 
-    def encode_copies_u8(self, frames, wm_rows, wm_table, out=None):
+    def encode_copies_u8(self, frames, wm_rows, wm_table, out=None, verify_len=None):
         """frames: CUDA uint8 [n, H, W, 3]; wm_rows: [C, n] rows of ``wm_table`` per copy and frame.  Returns the C marked copies
         [C, n, H, W, 3] in one pass (the frames are read and analyzed once); copy c equals
-        encode_frames_u8(frames, wm_rows=wm_rows[c], wm_table=wm_table) byte for byte."""
-        return self.engine.embed_copies(frames, wm_table, wm_rows, alpha=self.alpha, out=out)
+        encode_frames_u8(frames, wm_rows=wm_rows[c], wm_table=wm_table) byte for byte.  With ``verify_len`` (a payload length):
+        returns (copies, counts int32 [C, n, verify_len]), counts[c] being what a DctDecoder with this alpha reads from copy c
+        (decode_frames_u8), taken in the same pass."""
+        if verify_len is None:
+            return self.engine.embed_copies(frames, wm_table, wm_rows, alpha=self.alpha, out=out)
+        copies, counts, _bits = self.engine.embed_detect_copies(frames, wm_table, wm_rows, verify_len, alpha=self.alpha, out=out)
+        return copies, counts
 
     def encode_planes_yuv420(self, planes, height, width, out=None, wm_rows=None, wm_table=None, layout="i420"):
         """planes: CUDA uint8 [n, 1.5*H*W] (I420: Y|U|V per frame, NV12: Y|UV): the frame step on what a decoder produces

@@ -114,6 +114,17 @@ class DctEngine:
         nbytes = self.lib.ofmk_workspace_bytes(min(int(frames), _MAX_CHUNK_FRAMES), H, W)
         if nbytes == 0:
             raise _hip.HipError(f"bad frame size {H}x{W}")
+        return self._grown_ws(H, W, nbytes)
+
+    def copies_workspace(self, H: int, W: int, frames: int, copies: int):
+        """Scratch for embed_detect_copies with `frames` frames in flight: every copy keeps its own records next to the input's
+        (ofmk_copies_workspace_bytes).  The same one-buffer-per-frame-size cache as workspace(), which only grows."""
+        nbytes = self.lib.ofmk_copies_workspace_bytes(min(int(frames), _MAX_CHUNK_FRAMES), int(copies), H, W)
+        if nbytes == 0:
+            raise _hip.HipError(f"bad frame size {H}x{W} or copies {copies}")
+        return self._grown_ws(H, W, nbytes)
+
+    def _grown_ws(self, H, W, nbytes):
         ws = self._ws.get((H, W))
         if ws is None or ws.numel() < nbytes:
             ws = self.torch.empty(nbytes, dtype=self.torch.uint8, device=self.device)
@@ -208,15 +219,17 @@ class DctEngine:
             raise ValueError(f"out must be a contiguous CUDA {like.dtype} tensor of shape {shape} on {like.device}")
         return out
 
-    def _counts(self, counts, n, L):
+    def _counts(self, counts, n, L, copies=None):
         """The position sums of a call: a fresh int32 [n, L] tensor, or the caller's (a pipeline that hands them to another
-        stream keeps its own buffers: torch's allocator would hand a per-call tensor's block out again on the issuing stream)."""
+        stream keeps its own buffers: torch's allocator would hand a per-call tensor's block out again on the issuing stream).
+        ``copies``: one such array per copy, [copies, n, L]."""
         t = self.torch
+        shape = (n, L) if copies is None else (copies, n, L)
         if counts is None:
-            return t.empty((n, L), dtype=t.int32, device=self.device)
+            return t.empty(shape, dtype=t.int32, device=self.device)
         if not (isinstance(counts, t.Tensor) and counts.is_cuda and counts.device == self.device and counts.dtype == t.int32
-                and tuple(counts.shape) == (n, L) and counts.is_contiguous()):
-            raise ValueError(f"counts must be a contiguous CUDA int32 tensor of shape {(n, L)} on {self.device}")
+                and tuple(counts.shape) == shape and counts.is_contiguous()):
+            raise ValueError(f"counts must be a contiguous CUDA int32 tensor of shape {shape} on {self.device}")
         return counts
 
     def _soft(self, soft, n, L):
@@ -590,6 +603,32 @@ class DctEngine:
                                                        _hip.ptr(rows), float(alpha), cf, ws.data_ptr(), ws.numel(), stream, o))
         self._launch_marking(launch, frames, out, min(cf, n) * H * W * 3, False, chunks=-(-n // cf))
         return out
+
+    def embed_detect_copies(self, frames, wm, wm_rows, L, alpha=20, out=None, want_bits=False, counts=None, copies=None):
+        """embed_copies and the verify of every copy in the same pass: returns (out uint8 [C, n, H, W, 3], counts int32 [C, n, L],
+        bits uint8 [C, n, N] or None).  ``out`` is embed_copies' result byte for byte; counts[c] / bits[c] are what
+        ``embed_detect(frames, wm, L, alpha, wm_row=wm_rows[c])`` returns, i.e. ``detect(out[c], L, alpha)``.  Each copy is read out
+        from the pixels the mark kernel still holds, so no copy is read back (csrc/copies_kernels.hiph)."""
+        t = self.torch
+        n, H, W = self._check_frames(frames, t.uint8)
+        N = H * W // 64
+        wm = self._wm(wm, N)
+        rows, C = self._copy_rows(wm_rows, n, wm.shape[0], copies)
+        out = self._out(out, frames, (C, n, H, W, 3))
+        L = int(L)
+        counts = self._counts(counts, n, L, copies=C)
+        bits = t.empty((C, n, N), dtype=t.uint8, device=self.device) if want_bits else None
+        cf = self._chunk(n, H, W)
+        ws = self.copies_workspace(H, W, cf, C)
+        stream = _hip.current_stream()
+        fused = not (self.opts is not None and self.opts.flags & _hip.F_SEPARATE_DETECT)
+
+        def launch(o):
+            _hip.check(self.lib.ofmk_embed_detect_copies_rgb8(frames.data_ptr(), out.data_ptr(), C, n, H, W, wm.data_ptr(),
+                                                              wm.shape[0], _hip.ptr(rows), float(alpha), L, counts.data_ptr(),
+                                                              _hip.ptr(bits), cf, ws.data_ptr(), ws.numel(), stream, o))
+        self._launch_marking(launch, frames, out, min(cf, n) * H * W * 3, fused, chunks=-(-n // cf))
+        return out, counts, bits
 
     def svd_embed_copies(self, frames, wm, wm_rows, scale=15, scales=None, blk=4, out=None, L=None, want_bits=False, counts=None,
                          partial=False, copies=None):

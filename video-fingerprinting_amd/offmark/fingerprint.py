@@ -89,8 +89,12 @@ def identify_copies(segment_votes: dict, segment_numbers=None) -> list[int | Non
 
 def _reads_like(encoder, decoder) -> bool:
     """True when ``decoder`` reads exactly what the encoder's own verify reads: a DwtDctSvdDecoder with the encoder's channel-1
-    scale and blk (the DwtDctSvd read-out is channel 1's, dwt_dct_svd_decoder.py:24)."""
+    scale and blk (the DwtDctSvd read-out is channel 1's, dwt_dct_svd_decoder.py:24), or a DctDecoder with a DctEncoder's alpha."""
+    from .embed.dct_encoder import DctEncoder
+    from .extract.dct_decoder import DctDecoder
     from .extract.dwt_dct_svd_decoder import DwtDctSvdDecoder
+    if isinstance(encoder, DctEncoder):
+        return isinstance(decoder, DctDecoder) and encoder.alpha == decoder.alpha
     return (isinstance(decoder, DwtDctSvdDecoder) and getattr(encoder, "blk", None) == decoder.blk
             and getattr(encoder, "_scales", [None] * 3)[1] == decoder._scales[1])
 
@@ -156,7 +160,9 @@ def mark_segment_copies(encoder, decoder, frames, segment_of_frame, num_copies: 
     pattern covers fewer than ``min_frequency`` of the frames (mark_video_to_hls.py:381).
     An encoder offering ``encode_copies_u8`` marks all copies (up to 16) in one pass, and copies[c] are views of its result;
     a DwtDctSvdEncoder whose decoder reads with the same channel-1 scale and blk also hands over the verify's counts
-    (``encode_verify_copies_u8``).  Copies and sidecars are the same either way."""
+    (``encode_verify_copies_u8``), and so does a DctEncoder whose DctDecoder has the same alpha (``encode_copies_u8`` with
+    ``verify_len=8``): the decoder is then not called.  Copies and sidecars are the same either way."""
+    from .embed.dct_encoder import DctEncoder
     n, H, W, _ = frames.shape
     n_bits = decoder.bits_per_frame(H, W) if hasattr(decoder, "bits_per_frame") else H * W // 64      # DwtDctSvd(blk=8): H*W//256
     one_pass = None
@@ -165,6 +171,8 @@ def mark_segment_copies(encoder, decoder, frames, segment_of_frame, num_copies: 
         def one_pass(rows_dev, table_dev):
             if hasattr(encoder, "encode_verify_copies_u8") and _reads_like(encoder, decoder):
                 return encoder.encode_verify_copies_u8(frames, rows_dev, table_dev, 8)
+            if isinstance(encoder, DctEncoder) and _reads_like(encoder, decoder):
+                return encoder.encode_copies_u8(frames, rows_dev, table_dev, verify_len=8)
             return encoder.encode_copies_u8(frames, rows_dev, table_dev), None
     return _mark_copies(frames.device, n, H, W, n_bits, segment_of_frame, num_copies, key, min_frequency, one_pass,
                         lambda rows, table: encoder.encode_frames_u8(frames, wm_rows=rows, wm_table=table),
