@@ -324,6 +324,36 @@ int ofmk_embed_copies_yuv420(const uint8_t *in, uint8_t *out, int layout, int co
 int ofmk_svd_embed_copies_yuv420(const uint8_t *in, uint8_t *out, int layout, int copies, int n, int H, int W,
                                  const uint8_t *wm, int n_wm, const int32_t *wm_rows, const double *scales, int blk,
                                  int L, int32_t *counts, uint8_t *bits, void *stream, const ofmk_opts *opts);
+/* ---- the copies calls with the SOFT read-out of every copy in the same pass (BUILD EXTENSION, not reference semantics) --------
+ * Each call is its counterpart above -- ofmk_embed_detect_copies_rgb8, ofmk_svd_embed_copies_rgb8, ofmk_svd_embed_copies_yuv420 --
+ * with one more output after `bits`:
+ *   soft     device int64 [copies][n][L], required; L >= 1.  soft[c] is the stand-alone soft read-out of the written copy, integer
+ *            for integer: ofmk_detect_soft_rgb8(out[c], alpha), ofmk_svd_detect_soft_rgb8(out[c], scales, blk) and
+ *            ofmk_svd_detect_soft_yuv420(out[c], layout, scales, blk) respectively -- taken from the pixels (DwtDctSvd blk 4: the
+ *            verify's LL block and the stand-alone read-out's tight s0) or the block records (DCT codec) the copies kernels still hold,
+ *            so no written copy is read back.  Cleared by the call whatever it held.  scales[1] <= 0: all zeros.  No partial form.
+ *   out, counts, bits   exactly what the counterpart writes, byte for byte and integer for integer (OFMK_F_PARTIAL_COUNTS applies
+ *            to `counts` of the DwtDctSvd calls); counts and bits may BOTH be NULL here: the soft sums alone.
+ *   DCT codec: per chunk and copy the soft finalize of the copy's records next to the hard one (two small launches per copy,
+ *   kind 1); workspace of ofmk_copies_workspace_bytes; OFMK_F_SEPARATE_DETECT runs the literal sequence, ofmk_detect_soft_rgb8 of
+ *   each written copy included, with the same results.  DwtDctSvd blk 4: one fused launch for all copies, hard and soft sums
+ *   through an LDS histogram each (L > 2048: global atomics); blk 8: the single-copy launches and the stand-alone soft read-out
+ *   once per copy (the same results, no saving).  Launches are timed under the kinds of the counterparts.
+ *   With copies == 1 the results equal the single-copy embed (+ verify) plus the soft read-out of its output; nothing depends on
+ *   chunk_frames, the workspace size, the tile order or OFMK_F_SEPARATE_DETECT.  Arguments are checked before any HIP call
+ *   (OFMK_E_ARG): the counterpart's checks plus a non-NULL `soft` and L >= 1.  The calls only enqueue (no allocation, no
+ *   synchronisation), so they capture into a hipGraph. */
+int ofmk_embed_detect_copies_soft_rgb8(const uint8_t *in, uint8_t *out, int copies, int n, int H, int W,
+                                       const uint8_t *wm, int n_wm, const int32_t *wm_rows, double alpha,
+                                       int L, int32_t *counts, uint8_t *bits, long long *soft,
+                                       int chunk_frames, void *workspace, size_t workspace_bytes, void *stream,
+                                       const ofmk_opts *opts);
+int ofmk_svd_embed_copies_soft_rgb8(const uint8_t *in, uint8_t *out, int copies, int n, int H, int W,
+                                    const uint8_t *wm, int n_wm, const int32_t *wm_rows, const double *scales, int blk,
+                                    int L, int32_t *counts, uint8_t *bits, long long *soft, void *stream, const ofmk_opts *opts);
+int ofmk_svd_embed_copies_soft_yuv420(const uint8_t *in, uint8_t *out, int layout, int copies, int n, int H, int W,
+                                      const uint8_t *wm, int n_wm, const int32_t *wm_rows, const double *scales, int blk,
+                                      int L, int32_t *counts, uint8_t *bits, long long *soft, void *stream, const ofmk_opts *opts);
 int ofmk_yuv420_to_rgb8(const uint8_t *yuv, uint8_t *rgb, int layout, int n, int H, int W, void *stream,
                         const ofmk_opts *opts);
 int ofmk_rgb8_to_yuv420(const uint8_t *rgb, uint8_t *yuv, int layout, int n, int H, int W, void *stream,

@@ -569,6 +569,29 @@ int finalize_detect_copy(int q, int n, int f0, int cf, int H, int W, int L, doub
     return launch_finalize(a, cf, cx);
 }
 
+// The SOFT read-out of the same records (finalize_kernel<true>, the path ofmk_detect_soft_rgb8 takes after analyze) into the call's
+// int64 [copies][n][L] sums, cleared by the call.  A launch of its own: finalize's one LDS histogram serves the counts or the soft sums.
+int finalize_soft_copy(int q, int n, int f0, int cf, int H, int W, int L, double alpha, long long *soft, const CopiesWorkspace &ws,
+                       const Ctx &cx) {
+    FinArgs a = fin_base(ws.base, H, W, alpha);
+    a.rec = ws.rec + (size_t)q * ws.base.frames * a.nblk;
+    a.plane = ws.plane;
+    a.ysum = ws.ysum + (size_t)q * ws.base.frames * ws.base.tiles;
+    a.L = L;
+    a.soft = soft + ((size_t)q * n + f0) * L;
+    return launch_finalize(a, cf, cx);
+}
+
+// analyze + the soft finalize of frames [f0, f0+cf) of `in` ([n] frames; soft: their [n][L] sums, cleared by the caller)
+int detect_soft_chunk(const uint8_t *in, int f0, int cf, int H, int W, int L, double alpha, long long *soft, const Workspace &ws,
+                      const Ctx &cx) {
+    if (int rc = launch_analyze(in + (size_t)f0 * H * W * 3, SRC_RGB8, cf, H, W, ws, cx)) return rc;
+    FinArgs a = fin_base(ws, H, W, alpha);
+    a.L = L;
+    a.soft = soft + (size_t)f0 * L;
+    return launch_finalize(a, cf, cx);
+}
+
 // ---- planar YUV 4:2:0 (I420 / NV12) -------------------------------------------------------------
 int check_planar(int layout, int H, int W, const void *a, const void *b) {
     if (layout != OFMK_YUV_I420 && layout != OFMK_YUV_NV12) return fail(OFMK_E_ARG, "layout must be OFMK_YUV_I420 or OFMK_YUV_NV12%s");
@@ -914,8 +937,10 @@ int check_copies(const void *in, const void *out, int copies, int n, size_t fram
 
 // blk = 4: every copy from one launch per kMaxChunk frames; counts / bits of copy q at q * (the single-copy call's size).
 // a.wm_row is null: the rows come from wm_rows ([copies][n], or null = copy q marks with row q).
+// soft (optional): the call's int64 [copies][n][L] soft sums, cleared by the caller; a.L is then the payload length whether or not
+// counts / bits are asked for (svd_copies_soft_rgb8_kernel).
 int launch_svd_copies_rgb8(const uint8_t *in, uint8_t *out, int copies, int n, int H, int W, const int32_t *wm_rows, const SvdArgs &a,
-                           const Ctx &cx) {
+                           const Ctx &cx, long long *soft = nullptr) {
     const Geom g = svd_geom(H, W);
     const bool verify = a.counts || a.bits;
     const size_t count_rows = a.partial ? (size_t)svd_count_tiles(H, W, 4) : 1;
@@ -924,6 +949,14 @@ int launch_svd_copies_rgb8(const uint8_t *in, uint8_t *out, int copies, int n, i
         const CopyArgs kc = make_copy_args(copies, n, c.f0, wm_rows, g.frame_stride, count_rows * a.L, a.N);
         Geom gc = g;
         gc.frames = c.frames;
+        if (soft) {
+            const CopySoft sf{soft + (size_t)c.f0 * a.L, (size_t)n * a.L};
+            with_bool(al, [&](auto al_) { with_bool(c.multi, [&](auto mu) {
+                OFMK_TIMED_LAUNCH(c.timing, (svd_copies_soft_rgb8_kernel<decltype(al_)::value, decltype(mu)::value>), c.grid, dim3(kThreads), 0, cx.s,
+                                  in + c.offset, out + c.offset, gc, c.a, kc, sf);
+            }); });
+            return;
+        }
         with_bool(al, [&](auto al_) { with_bool(verify, [&](auto vf) { with_bool(c.multi, [&](auto mu) {
             OFMK_TIMED_LAUNCH(c.timing, (svd_copies_rgb8_kernel<decltype(al_)::value, decltype(vf)::value, decltype(mu)::value>), c.grid, dim3(kThreads), 0, cx.s,
                               in + c.offset, out + c.offset, gc, c.a, kc);
@@ -950,17 +983,49 @@ int launch_mark_copies_yuv420(const uint8_t *in, uint8_t *out, int layout, int c
 }
 
 // blk = 4 on planes: every copy from one launch per kMaxChunk frames, as launch_svd_copies_rgb8 (H and W multiples of 8: no fringe).
+// soft: as launch_svd_copies_rgb8 (svd_copies_soft_yuv420_kernel).
 int launch_svd_copies_yuv420(const uint8_t *in, uint8_t *out, int layout, int copies, int n, int H, int W, const int32_t *wm_rows,
-                             const SvdArgs &a, const Ctx &cx) {
+                             const SvdArgs &a, const Ctx &cx, long long *soft = nullptr) {
     const PGeom g = make_pgeom(layout, H, W, 0);
     const bool verify = a.counts || a.bits;
     const size_t count_rows = a.partial ? (size_t)svd_count_tiles(H, W, 4) : 1;
     return launch_svd({g.nblk, a.N, g.frame_stride, copies}, n, a, cx, [&](SvdChunk &c) {
         const CopyArgs kc = make_copy_args(copies, n, c.f0, wm_rows, g.frame_stride, count_rows * a.L, a.N);
+        if (soft) {
+            const CopySoft sf{soft + (size_t)c.f0 * a.L, (size_t)n * a.L};
+            with_fmt(layout, [&](auto fmt) { with_bool(c.multi, [&](auto mu) {
+                OFMK_TIMED_LAUNCH(c.timing, (svd_copies_soft_yuv420_kernel<decltype(fmt)::value, decltype(mu)::value>), c.grid, dim3(kThreads), 0, cx.s,
+                                  in + c.offset, out + c.offset, g, c.frames, c.a, kc, sf);
+            }); });
+            return;
+        }
         with_fmt(layout, [&](auto fmt) { with_bool(verify, [&](auto vf) { with_bool(c.multi, [&](auto mu) {
             OFMK_TIMED_LAUNCH(c.timing, (svd_copies_yuv420_kernel<decltype(fmt)::value, decltype(vf)::value, decltype(mu)::value>), c.grid, dim3(kThreads), 0, cx.s,
                               in + c.offset, out + c.offset, g, c.frames, c.a, kc);
         }); }); });
+    });
+}
+
+// The host half of ofmk_svd_embed_copies_soft_*: the hard copies call plus the int64 [copies][n][L] soft sums of every written copy.
+// Arguments are checked by the caller; a is the hard call's SvdArgs.  scales[1] <= 0: the hard call's route, soft stays zero.
+// blk 4: fused(a, soft) is the copies launcher (soft null: its hard form); blk 8: single(out_q, b) is the single-copy embed (+ verify)
+// launcher on copy q, and soft_of(out_q, b) the stand-alone soft read-out of that written copy (b.counts carries the int64 sums).
+template <class Fused, class Single, class SoftOf>
+int svd_copies_soft(uint8_t *out, size_t frame_bytes, int copies, int n, int H, int W, int blk, int L, const int32_t *wm_rows, SvdArgs a,
+                    long long *soft, const Ctx &cx, Fused &&fused, Single &&single, SoftOf &&soft_of) {
+    a.L = L;                                           // also without counts / bits: the soft sums' row length
+    HIP_TRY(launch_zero(soft, (size_t)copies * n * L * sizeof(long long), cx.s));
+    const bool on = a.scales[1] > 0.f;
+    if (blk == 4) return fused(a, on ? soft : nullptr);
+    return launch_svd8_copies(out, frame_bytes, copies, n, H, W, wm_rows, a, [&](uint8_t *out_q, const SvdArgs &b) {
+        if (int rc = single(out_q, b)) return rc;
+        if (!on) return (int)OFMK_OK;
+        const size_t q = (size_t)(out_q - out) / ((size_t)n * frame_bytes);
+        SvdArgs bs = b;
+        bs.counts = reinterpret_cast<int32_t *>(soft + q * n * L);
+        bs.bits = nullptr;
+        bs.partial = 0;
+        return soft_of(out_q, bs);
     });
 }
 
@@ -1012,14 +1077,7 @@ int ofmk_detect_soft_rgb8(const uint8_t *in, int n, int H, int W, int L, double 
     if ((rc = carve(workspace, workspace_bytes, H, W, chunk_frames, ws))) return rc;
     const Ctx cx = make_ctx(stream, opts);
     HIP_TRY(launch_zero(soft, (size_t)n * L * sizeof(long long), cx.s));
-    const size_t fs = (size_t)H * W * 3;
-    return for_chunks(n, ws.frames, [&](int f0, int cf) {
-        if (int rc = launch_analyze(in + (size_t)f0 * fs, SRC_RGB8, cf, H, W, ws, cx)) return rc;
-        FinArgs a = fin_base(ws, H, W, alpha);
-        a.L = L;
-        a.soft = soft + (size_t)f0 * L;
-        return launch_finalize(a, cf, cx);
-    });
+    return for_chunks(n, ws.frames, [&](int f0, int cf) { return detect_soft_chunk(in, f0, cf, H, W, L, alpha, soft, ws, cx); });
 }
 
 int ofmk_embed_detect_rgb8(const uint8_t *in, uint8_t *out, int n, int H, int W, const uint8_t *wm, int n_wm,
@@ -1216,6 +1274,66 @@ int ofmk_embed_detect_copies_rgb8(const uint8_t *in, uint8_t *out, int copies, i
     });
     if (rc) return rc;
     return launch_copy_fringe_copies(in, out, copies, n, H, W, cx.s);
+}
+
+int ofmk_embed_detect_copies_soft_rgb8(const uint8_t *in, uint8_t *out, int copies, int n, int H, int W, const uint8_t *wm, int n_wm,
+                                       const int32_t *wm_rows, double alpha, int L, int32_t *counts, uint8_t *bits, long long *soft,
+                                       int chunk_frames, void *workspace, size_t workspace_bytes, void *stream, const ofmk_opts *opts) {
+    if (int orc = check_opts(opts)) return orc;
+    int rc = check_embed_args(in, out, n, H, W, wm, n_wm);
+    if (rc) return rc;
+    if ((rc = check_copies(in, out, copies, n, (size_t)H * W * 3))) return rc;
+    if ((rc = check_soft_args(out, n, H, W, L, soft))) return rc;
+    CopiesWorkspace ws;
+    if ((rc = carve_copies(workspace, workspace_bytes, copies, H, W, chunk_frames, ws))) return rc;
+    const Ctx cx = make_ctx(stream, opts);
+    const bool hard = counts || bits;
+    const size_t fs = (size_t)H * W * 3;
+    const size_t N = (size_t)((long long)H * W / 64);
+    HIP_TRY(launch_zero(soft, (size_t)copies * n * L * sizeof(long long), cx.s));
+    rc = for_chunks(n, ws.base.frames, [&](int f0, int cf) {      // one analysis of the input per chunk serves every copy
+        if (int rc = launch_analyze(in + (size_t)f0 * fs, SRC_RGB8, cf, H, W, ws.base, cx)) return rc;
+        if (!(cx.flags & OFMK_F_SEPARATE_DETECT)) {
+            if (int rc = launch_mark_verify_copies_rgb8(in, out, copies, n, f0, cf, H, W, wm, n_wm, wm_rows, alpha, L, counts, ws, cx)) return rc;
+            for (int q = 0; q < copies; ++q) {                    // two small launches per copy on the records the fused launch left
+                if (hard)
+                    if (int rc = finalize_detect_copy(q, n, f0, cf, H, W, L, alpha, counts, bits, ws, cx)) return rc;
+                if (int rc = finalize_soft_copy(q, n, f0, cf, H, W, L, alpha, soft, ws, cx)) return rc;
+            }
+            return (int)OFMK_OK;
+        }
+        // the literal sequence: mark every copy, then detect and soft-detect each written copy
+        if (int rc = launch_mark_copies_rgb8(in, out, copies, n, f0, cf, H, W, wm, n_wm, wm_rows, alpha, ws.base, cx)) return rc;
+        for (int q = 0; q < copies; ++q) {
+            const uint8_t *out_q = out + (size_t)q * n * fs;
+            if (hard)
+                if (int rc = detect_chunk(out_q, SRC_RGB8, f0, cf, H, W, L, alpha, counts ? counts + (size_t)q * n * L : nullptr,
+                                          bits ? bits + (size_t)q * n * N : nullptr, ws.base, cx)) return rc;
+            if (int rc = detect_soft_chunk(out_q, f0, cf, H, W, L, alpha, soft + (size_t)q * n * L, ws.base, cx)) return rc;
+        }
+        return (int)OFMK_OK;
+    });
+    if (rc) return rc;
+    return launch_copy_fringe_copies(in, out, copies, n, H, W, cx.s);
+}
+
+int ofmk_svd_embed_copies_soft_rgb8(const uint8_t *in, uint8_t *out, int copies, int n, int H, int W, const uint8_t *wm, int n_wm,
+                                    const int32_t *wm_rows, const double *scales, int blk, int L, int32_t *counts, uint8_t *bits,
+                                    long long *soft, void *stream, const ofmk_opts *opts) {
+    if (int orc = check_opts(opts)) return orc;
+    int rc = check_embed_args(in, out, n, H, W, wm, n_wm);
+    if (rc) return rc;
+    if ((rc = check_copies(in, out, copies, n, (size_t)H * W * 3))) return rc;
+    if ((rc = check_blk(blk))) return rc;
+    if ((rc = check_soft_args(out, n, H, W, L, soft))) return rc;
+    SvdArgs a;
+    if ((rc = make_svd_args(a, H, W, scales, false, wm, n_wm, nullptr, L, counts, bits, opts))) return rc;
+    const int mode = counts || bits ? SVD_EMBED_VERIFY : SVD_EMBED;
+    const Ctx cx = make_ctx(stream, opts);
+    return svd_copies_soft(out, (size_t)H * W * 3, copies, n, H, W, blk, L, wm_rows, a, soft, cx,
+        [&](const SvdArgs &b, long long *sf) { return launch_svd_copies_rgb8(in, out, copies, n, H, W, wm_rows, b, cx, sf); },
+        [&](uint8_t *out_q, const SvdArgs &b) { return launch_svd_rgb8(in, out_q, n, H, W, mode, 8, b, cx); },
+        [&](uint8_t *out_q, const SvdArgs &b) { return launch_svd_rgb8(out_q, nullptr, n, H, W, SVD_DETECT_SOFT, 8, b, cx); });
 }
 
 int ofmk_svd_embed_copies_rgb8(const uint8_t *in, uint8_t *out, int copies, int n, int H, int W, const uint8_t *wm, int n_wm,
@@ -1476,6 +1594,27 @@ int ofmk_svd_embed_copies_yuv420(const uint8_t *in, uint8_t *out, int layout, in
     const int mode = counts || bits ? SVD_EMBED_VERIFY : SVD_EMBED;         // per copy: the tiles, then the fringe's 4:2:0 round trip
     return launch_svd8_copies(out, fs, copies, n, H, W, wm_rows, a,
                               [&](uint8_t *out_q, const SvdArgs &b) { return launch_svd_yuv420(in, out_q, layout, n, H, W, mode, 8, b, cx); });
+}
+
+int ofmk_svd_embed_copies_soft_yuv420(const uint8_t *in, uint8_t *out, int layout, int copies, int n, int H, int W, const uint8_t *wm,
+                                      int n_wm, const int32_t *wm_rows, const double *scales, int blk, int L, int32_t *counts,
+                                      uint8_t *bits, long long *soft, void *stream, const ofmk_opts *opts) {
+    if (int orc = check_opts(opts)) return orc;
+    int rc = check_embed_args(in, out, n, H, W, wm, n_wm);
+    if (rc) return rc;
+    if ((rc = check_blk(blk))) return rc;
+    if ((rc = check_planar(layout, H, W, in, out))) return rc;
+    const size_t fs = (size_t)H * W * 3 / 2;
+    if ((rc = check_copies(in, out, copies, n, fs))) return rc;
+    if ((rc = check_soft_args(out, n, H, W, L, soft))) return rc;
+    SvdArgs a;
+    if ((rc = make_svd_args(a, H, W, scales, false, wm, n_wm, nullptr, L, counts, bits, opts))) return rc;
+    const int mode = counts || bits ? SVD_EMBED_VERIFY : SVD_EMBED;
+    const Ctx cx = make_ctx(stream, opts);
+    return svd_copies_soft(out, fs, copies, n, H, W, blk, L, wm_rows, a, soft, cx,
+        [&](const SvdArgs &b, long long *sf) { return launch_svd_copies_yuv420(in, out, layout, copies, n, H, W, wm_rows, b, cx, sf); },
+        [&](uint8_t *out_q, const SvdArgs &b) { return launch_svd_yuv420(in, out_q, layout, n, H, W, mode, 8, b, cx); },
+        [&](uint8_t *out_q, const SvdArgs &b) { return launch_svd_yuv420(out_q, nullptr, layout, n, H, W, SVD_DETECT_SOFT, 8, b, cx); });
 }
 
 int ofmk_yuv420_to_rgb8(const uint8_t *yuv, uint8_t *rgb, int layout, int n, int H, int W, void *stream, const ofmk_opts *opts) {

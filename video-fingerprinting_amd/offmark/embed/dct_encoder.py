@@ -82,14 +82,21 @@ class DctEncoder:
         wm = wm_table if wm_table is not None else self._device_wm(h * w // 64)
         return self.engine.embed(frames, wm, alpha=self.alpha, wm_row=wm_rows, out=out)
 
-    def encode_copies_u8(self, frames, wm_rows, wm_table, out=None, verify_len=None):
+    def encode_copies_u8(self, frames, wm_rows, wm_table, out=None, verify_len=None, soft=False):
         """frames: CUDA uint8 [n, H, W, 3]; wm_rows: [C, n] rows of ``wm_table`` per copy and frame.  Returns the C marked copies
         [C, n, H, W, 3] in one pass (the frames are read and analyzed once); copy c equals
         encode_frames_u8(frames, wm_rows=wm_rows[c], wm_table=wm_table) byte for byte.  With ``verify_len`` (a payload length):
         returns (copies, counts int32 [C, n, verify_len]), counts[c] being what a DctDecoder with this alpha reads from copy c
-        (decode_frames_u8), taken in the same pass."""
+        (decode_frames_u8), taken in the same pass.  With ``soft=True`` as well: (copies, counts, soft int64 [C, n, verify_len]),
+        soft[c] being that decoder's decode_soft_frames_u8 of copy c, from the same pass."""
         if verify_len is None:
+            if soft:
+                raise ValueError("soft=True needs verify_len (the payload length)")
             return self.engine.embed_copies(frames, wm_table, wm_rows, alpha=self.alpha, out=out)
+        if soft:
+            copies, counts, _bits, sums = self.engine.embed_detect_copies(frames, wm_table, wm_rows, verify_len, alpha=self.alpha,
+                                                                          out=out, soft=True)
+            return copies, counts, sums
         copies, counts, _bits = self.engine.embed_detect_copies(frames, wm_table, wm_rows, verify_len, alpha=self.alpha, out=out)
         return copies, counts
 

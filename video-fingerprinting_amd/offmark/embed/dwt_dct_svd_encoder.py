@@ -92,10 +92,15 @@ class DwtDctSvdEncoder:
         encode_frames_u8(frames, wm_rows=wm_rows[c], wm_table=wm_table) byte for byte."""
         return self.engine.svd_embed_copies(frames, wm_table, wm_rows, scales=self._scales, blk=self.blk, out=out)
 
-    def encode_verify_copies_u8(self, frames, wm_rows, wm_table, payload_len, out=None):
+    def encode_verify_copies_u8(self, frames, wm_rows, wm_table, payload_len, out=None, soft=False):
         """encode_copies_u8 plus the read-out of every written copy with this encoder's channel-1 scale and blk: returns
         (copies [C, n, H, W, 3], counts int32 [C, n, payload_len]); counts[c] equals what a DwtDctSvdDecoder with the same
-        channel-1 scale and blk returns from decode_frames_u8(copies[c], payload_len)."""
+        channel-1 scale and blk returns from decode_frames_u8(copies[c], payload_len).  ``soft=True``: (copies, counts, soft int64
+        [C, n, payload_len]), soft[c] being that decoder's decode_soft_frames_u8 of copy c, from the same pass."""
+        if soft:
+            out, counts, _, sums = self.engine.svd_embed_copies(frames, wm_table, wm_rows, scales=self._scales, blk=self.blk, out=out,
+                                                                L=int(payload_len), soft=True)
+            return out, counts, sums
         out, counts, _ = self.engine.svd_embed_copies(frames, wm_table, wm_rows, scales=self._scales, blk=self.blk, out=out,
                                                       L=int(payload_len))
         return out, counts
@@ -115,10 +120,17 @@ class DwtDctSvdEncoder:
         return self.engine.svd_embed_copies_yuv420(planes, height, width, wm_table, wm_rows, scales=self._scales, blk=self.blk,
                                                    out=out, layout=layout)
 
-    def encode_verify_copies_planes_yuv420(self, planes, height, width, wm_rows, wm_table, payload_len, out=None, layout="i420"):
+    def encode_verify_copies_planes_yuv420(self, planes, height, width, wm_rows, wm_table, payload_len, out=None, layout="i420",
+                                           soft=False):
         """encode_copies_planes_yuv420 plus the read-out of every written copy with this encoder's channel-1 scale and blk:
         returns (copies [C, n, 1.5*H*W], counts int32 [C, n, payload_len]); counts[c] equals what a DwtDctSvdDecoder with the
-        same channel-1 scale and blk returns from decode_planes_yuv420(copies[c], height, width, payload_len)."""
+        same channel-1 scale and blk returns from decode_planes_yuv420(copies[c], height, width, payload_len).  ``soft=True``:
+        (copies, counts, soft int64 [C, n, payload_len]), soft[c] being that decoder's decode_soft_planes_yuv420 of copy c."""
+        if soft:
+            out, counts, _, sums = self.engine.svd_embed_copies_yuv420(planes, height, width, wm_table, wm_rows, scales=self._scales,
+                                                                       blk=self.blk, out=out, L=int(payload_len), layout=layout,
+                                                                       soft=True)
+            return out, counts, sums
         out, counts, _ = self.engine.svd_embed_copies_yuv420(planes, height, width, wm_table, wm_rows, scales=self._scales,
                                                              blk=self.blk, out=out, L=int(payload_len), layout=layout)
         return out, counts

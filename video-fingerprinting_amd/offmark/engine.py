@@ -232,14 +232,16 @@ class DctEngine:
             raise ValueError(f"counts must be a contiguous CUDA int32 tensor of shape {shape} on {self.device}")
         return counts
 
-    def _soft(self, soft, n, L):
-        """The soft sums of a call: a fresh int64 [n, L] tensor, or the caller's (whatever it holds: the library clears it)."""
+    def _soft(self, soft, n, L, copies=None):
+        """The soft sums of a call: a fresh int64 [n, L] tensor, or the caller's (whatever it holds: the library clears it).
+        ``copies``: one such array per copy, [copies, n, L]; ``soft`` may then be True (a fresh tensor)."""
         t = self.torch
-        if soft is None:
-            return t.empty((n, L), dtype=t.int64, device=self.device)
+        shape = (n, L) if copies is None else (copies, n, L)
+        if soft is None or soft is True:
+            return t.empty(shape, dtype=t.int64, device=self.device)
         if not (isinstance(soft, t.Tensor) and soft.is_cuda and soft.device == self.device and soft.dtype == t.int64
-                and tuple(soft.shape) == (n, L) and soft.is_contiguous()):
-            raise ValueError(f"soft must be a contiguous CUDA int64 tensor of shape {(n, L)} on {self.device}")
+                and tuple(soft.shape) == shape and soft.is_contiguous()):
+            raise ValueError(f"soft must be a contiguous CUDA int64 tensor of shape {shape} on {self.device}")
         return soft
 
     def _layout(self, layout):
@@ -604,11 +606,13 @@ class DctEngine:
         self._launch_marking(launch, frames, out, min(cf, n) * H * W * 3, False, chunks=-(-n // cf))
         return out
 
-    def embed_detect_copies(self, frames, wm, wm_rows, L, alpha=20, out=None, want_bits=False, counts=None, copies=None):
+    def embed_detect_copies(self, frames, wm, wm_rows, L, alpha=20, out=None, want_bits=False, counts=None, copies=None, soft=None):
         """embed_copies and the verify of every copy in the same pass: returns (out uint8 [C, n, H, W, 3], counts int32 [C, n, L],
         bits uint8 [C, n, N] or None).  ``out`` is embed_copies' result byte for byte; counts[c] / bits[c] are what
         ``embed_detect(frames, wm, L, alpha, wm_row=wm_rows[c])`` returns, i.e. ``detect(out[c], L, alpha)``.  Each copy is read out
-        from the pixels the mark kernel still holds, so no copy is read back (csrc/copies_kernels.hiph)."""
+        from the pixels the mark kernel still holds, so no copy is read back (csrc/copies_kernels.hiph).
+        ``soft`` (build extension): True or an int64 [C, n, L] tensor -- also the soft sums of every copy, soft[c] ==
+        ``detect_soft(out[c], L, alpha)``, from the same records; returned as a fourth element."""
         t = self.torch
         n, H, W = self._check_frames(frames, t.uint8)
         N = H * W // 64
@@ -623,18 +627,30 @@ class DctEngine:
         stream = _hip.current_stream()
         fused = not (self.opts is not None and self.opts.flags & _hip.F_SEPARATE_DETECT)
 
+        want_soft = soft is not None and soft is not False
+        if want_soft:
+            soft = self._soft(soft, n, L, copies=C)
+
         def launch(o):
+            if want_soft:
+                _hip.check(self.lib.ofmk_embed_detect_copies_soft_rgb8(frames.data_ptr(), out.data_ptr(), C, n, H, W, wm.data_ptr(),
+                                                                       wm.shape[0], _hip.ptr(rows), float(alpha), L, counts.data_ptr(),
+                                                                       _hip.ptr(bits), soft.data_ptr(), cf, ws.data_ptr(), ws.numel(),
+                                                                       stream, o))
+                return
             _hip.check(self.lib.ofmk_embed_detect_copies_rgb8(frames.data_ptr(), out.data_ptr(), C, n, H, W, wm.data_ptr(),
                                                               wm.shape[0], _hip.ptr(rows), float(alpha), L, counts.data_ptr(),
                                                               _hip.ptr(bits), cf, ws.data_ptr(), ws.numel(), stream, o))
         self._launch_marking(launch, frames, out, min(cf, n) * H * W * 3, fused, chunks=-(-n // cf))
-        return out, counts, bits
+        return (out, counts, bits, soft) if want_soft else (out, counts, bits)
 
     def svd_embed_copies(self, frames, wm, wm_rows, scale=15, scales=None, blk=4, out=None, L=None, want_bits=False, counts=None,
-                         partial=False, copies=None):
+                         partial=False, copies=None, soft=None):
         """The DwtDctSvd codec's copies in one pass: copy c of the uint8 [C, n, H, W, 3] result equals ``svd_embed`` with
         ``wm_row=wm_rows[c]``.  With ``L``: also the verify of every copy, returns (out, counts [C, n, L] -- or, ``partial``,
-        [C, n, tiles, L] -- and bits [C, n, bits_per_frame] or None), each copy's equal to ``svd_embed_detect``'s."""
+        [C, n, tiles, L] -- and bits [C, n, bits_per_frame] or None), each copy's equal to ``svd_embed_detect``'s.
+        ``soft`` (build extension, needs ``L``): True or an int64 [C, n, L] tensor -- also the soft sums of every copy, soft[c] ==
+        ``svd_detect_soft(out[c], L, ...)``, from the pixels the kernel still holds (blk 4); returned as a fourth element."""
         t = self.torch
         n, H, W = self._check_frames(frames, t.uint8)
         wm = self._wm(wm, H * W // 64)
@@ -645,6 +661,15 @@ class DctEngine:
             counts, flag = self._svd_counts(counts, n, H, W, L, blk, partial, copies=C)
             if want_bits:
                 bits = t.empty((C, n, self.svd_bits_per_frame(H, W, blk)), dtype=t.uint8, device=self.device)
+        if soft is not None and soft is not False:
+            if L is None:
+                raise ValueError("soft needs the payload length L")
+            soft = self._soft(soft, n, int(L), copies=C)
+            _hip.check(self.lib.ofmk_svd_embed_copies_soft_rgb8(frames.data_ptr(), out.data_ptr(), C, n, H, W, wm.data_ptr(), wm.shape[0],
+                                                                _hip.ptr(rows), _hip.scales3(scale, scales), int(blk), int(L),
+                                                                _hip.ptr(counts), _hip.ptr(bits), soft.data_ptr(), _hip.current_stream(),
+                                                                self._o(extra_flags=flag)))
+            return out, counts, bits, soft
         _hip.check(self.lib.ofmk_svd_embed_copies_rgb8(frames.data_ptr(), out.data_ptr(), C, n, H, W, wm.data_ptr(), wm.shape[0],
                                                        _hip.ptr(rows), _hip.scales3(scale, scales), int(blk),
                                                        int(L) if L is not None else 0, _hip.ptr(counts) if L is not None else None,
@@ -720,11 +745,12 @@ class DctEngine:
         return out
 
     def svd_embed_copies_yuv420(self, planes, H, W, wm, wm_rows, scale=15, scales=None, blk=4, out=None, L=None, want_bits=False,
-                                counts=None, partial=False, copies=None, layout="i420"):
+                                counts=None, partial=False, copies=None, layout="i420", soft=None):
         """The DwtDctSvd codec's copies on 4:2:0 planes in one pass: copy c of the uint8 [C, n, 1.5*H*W] result equals
         ``svd_embed_yuv420`` with ``wm_row=wm_rows[c]``.  With ``L``: also the verify of every copy, returns (out, counts [C, n, L]
         -- or, ``partial``, [C, n, tiles, L] -- and bits [C, n, bits_per_frame] or None), each copy's equal to
-        ``svd_embed_detect_yuv420``'s."""
+        ``svd_embed_detect_yuv420``'s.  ``soft`` (build extension, needs ``L``): True or an int64 [C, n, L] tensor -- also soft[c] ==
+        ``svd_detect_soft_yuv420(out[c], ...)``, returned as a fourth element."""
         t = self.torch
         n = self._check_planar(planes, H, W)
         fmt = self._layout(layout)
@@ -736,6 +762,15 @@ class DctEngine:
             counts, flag = self._svd_counts(counts, n, H, W, L, blk, partial, copies=C)
             if want_bits:
                 bits = t.empty((C, n, self.svd_bits_per_frame(H, W, blk)), dtype=t.uint8, device=self.device)
+        if soft is not None and soft is not False:
+            if L is None:
+                raise ValueError("soft needs the payload length L")
+            soft = self._soft(soft, n, int(L), copies=C)
+            _hip.check(self.lib.ofmk_svd_embed_copies_soft_yuv420(planes.data_ptr(), out.data_ptr(), fmt, C, n, H, W, wm.data_ptr(),
+                                                                  wm.shape[0], _hip.ptr(rows), _hip.scales3(scale, scales), int(blk), int(L),
+                                                                  _hip.ptr(counts), _hip.ptr(bits), soft.data_ptr(),
+                                                                  _hip.current_stream(), self._o(extra_flags=flag)))
+            return out, counts, bits, soft
         _hip.check(self.lib.ofmk_svd_embed_copies_yuv420(planes.data_ptr(), out.data_ptr(), fmt, C, n, H, W, wm.data_ptr(),
                                                          wm.shape[0], _hip.ptr(rows), _hip.scales3(scale, scales), int(blk),
                                                          int(L) if L is not None else 0, _hip.ptr(counts) if L is not None else None,

@@ -99,11 +99,49 @@ def _reads_like(encoder, decoder) -> bool:
             and getattr(encoder, "_scales", [None] * 3)[1] == decoder._scales[1])
 
 
-def _mark_copies(device, n, H, W, n_bits, segment_of_frame, num_copies, key, min_frequency, one_pass, one_copy, read):
+def copy_margins(soft, segment_of_frame, expected_raw_bits, units_per_frame: int) -> dict:
+    """How far every segment of ONE marked copy is from flipping a payload position (build extension, from the soft read-outs).
+
+    soft: int64 [n, L] soft sums of the copy's frames (2^14 fixed point, positive reads as 1: decode_soft_frames_u8 /
+    decode_soft_planes_yuv420, or the one-pass copies calls' ``soft[c]``), tensor or array; segment_of_frame: int [n];
+    expected_raw_bits: {segment: the L bits written at raw positions 0..L-1} -- the first L entries of the segment's watermark
+    row, i.e. the shuffled payload before the key permutation is undone; units_per_frame: U, the units a frame reads out
+    ((H/8)*(W/8) for the DCT codec and DwtDctSvd blk 4, the 16x16 tile count for blk 8).
+    With T[i] the sum of soft[f][i] over the segment's frames and K[i] the number of units u < U with u mod L == i,
+        margin = min over i of (2 e[i] - 1) T[i] / (16384 K[i] frames),   float64, in [-1, 1]
+    (positions no unit lands on, K[i] == 0, are left out): 1 = every unit sits on its lattice point, <= 0 = some position does
+    not read as written.  Returns {segment: margin}."""
+    sums = soft.cpu().numpy() if hasattr(soft, "cpu") else np.asarray(soft)
+    sums = sums.astype(np.int64)
+    seg = np.asarray(segment_of_frame)
+    L = sums.shape[1]
+    pos = np.arange(L)
+    K = np.where(pos < units_per_frame, (units_per_frame - pos + L - 1) // L, 0).astype(np.float64)
+    out = {}
+    for s, e in expected_raw_bits.items():
+        rows = sums[seg == s]
+        T = rows.sum(axis=0).astype(np.float64)
+        sign = 2.0 * np.asarray(e, dtype=np.float64).reshape(-1)[:L] - 1.0
+        used = K > 0
+        out[s] = float(np.min(sign[used] * T[used] / (16384.0 * K[used] * rows.shape[0])))
+    return out
+
+
+def units_per_frame(decoder, height: int, width: int) -> int:
+    """Units a frame reads out: 16x16 tiles for a DwtDctSvd decoder with blk 8, else 8x8 pixel blocks."""
+    if getattr(decoder, "blk", 4) == 8:
+        return ((height // 4 * 2) // 8) * ((width // 4 * 2) // 8)
+    return (height // 8) * (width // 8)
+
+
+def _mark_copies(device, n, H, W, n_bits, segment_of_frame, num_copies, key, min_frequency, one_pass, one_copy, read,
+                 read_soft=None, units=0):
     """The bookkeeping mark_segment_copies and mark_segment_copies_yuv420 share: watermark table and rows of every (segment, copy),
     the marking (``one_pass(rows_dev [C, n], table_dev)`` -> (marked [C, ...], counts [C, n, 8] or None), or None when the
     encoder has no one-pass call; then ``one_copy(rows_dev [n], table_dev)`` per copy), the vote of every copy
-    (``read(marked)`` -> counts where the marking left none) and the sidecar dicts."""
+    (``read(marked)`` -> counts where the marking left none) and the sidecar dicts.  ``read_soft`` (margins): one_pass may return
+    the copies' soft sums [C, n, 8] as a third element, ``read_soft(marked)`` gives them where it does not, and the sidecars gain
+    "segment_margins" (copy_margins with ``units`` units per frame)."""
     import torch
     from .degenerator.de_shuffler import DeShuffler
     from .dist.vote import vote_segments
@@ -120,9 +158,11 @@ def _mark_copies(device, n, H, W, n_bits, segment_of_frame, num_copies, key, min
     copies, segment_payloads, failed = [], {}, []
     segment_copies = {str(s): [] for s in segments}
     rows_all = np.array([[index[(int(s), c)] for s in seg] for c in range(num_copies)], dtype=np.int32).reshape(num_copies, n)
-    marked_all = counts_all = None
+    marked_all = counts_all = soft_all = None
+    segment_margins = {}
     if one_pass is not None and 1 <= num_copies <= 16:
-        marked_all, counts_all = one_pass(torch.from_numpy(rows_all).to(device), table_dev)
+        marked_all, counts_all, *rest = one_pass(torch.from_numpy(rows_all).to(device), table_dev)
+        soft_all = rest[0] if rest else None
     for c in range(num_copies):
         if marked_all is not None:
             marked = marked_all[c]
@@ -131,6 +171,10 @@ def _mark_copies(device, n, H, W, n_bits, segment_of_frame, num_copies, key, min
         counts = counts_all[c] if counts_all is not None else read(marked)
         votes = vote_segments(deg.degenerate_counts(counts.cpu().numpy(), n_bits), seg)
         copies.append(marked)
+        if read_soft is not None:
+            sums = soft_all[c] if soft_all is not None else read_soft(marked)
+            per_segment = copy_margins(sums, seg, {s: table[index[(s, c)], :8] for s in segments}, units)
+            segment_margins.update({f"{s}_{c}": per_segment[s] for s in segments})
         for s in segments:
             payload = payload_for_segment(s, c).tolist()
             name = f"marked_seg{s}_copy{c}.mp4"
@@ -146,10 +190,14 @@ def _mark_copies(device, n, H, W, n_bits, segment_of_frame, num_copies, key, min
                            "total_marked_segments": len(segments) * num_copies, "segments": segment_copies},
         "failed_segments": failed,
     }
+    if read_soft is not None:
+        sidecars["segment_margins"] = segment_margins
     return copies, sidecars
 
 
-def mark_segment_copies(encoder, decoder, frames, segment_of_frame, num_copies: int, key=0, min_frequency: float = 0.5):
+
+def mark_segment_copies(encoder, decoder, frames, segment_of_frame, num_copies: int, key=0, min_frequency: float = 0.5,
+                        margins: bool = False):
     """Mark ``num_copies`` versions of every segment and verify each one.
 
     encoder / decoder: HIP codecs offering ``encode_frames_u8`` / ``decode_frames_u8`` (DctEncoder+DctDecoder or
@@ -161,7 +209,11 @@ def mark_segment_copies(encoder, decoder, frames, segment_of_frame, num_copies: 
     An encoder offering ``encode_copies_u8`` marks all copies (up to 16) in one pass, and copies[c] are views of its result;
     a DwtDctSvdEncoder whose decoder reads with the same channel-1 scale and blk also hands over the verify's counts
     (``encode_verify_copies_u8``), and so does a DctEncoder whose DctDecoder has the same alpha (``encode_copies_u8`` with
-    ``verify_len=8``): the decoder is then not called.  Copies and sidecars are the same either way."""
+    ``verify_len=8``): the decoder is then not called.  Copies and sidecars are the same either way.
+    ``margins=True`` (build extension): the sidecars gain "segment_margins": {"<segment>_<copy>": copy_margins' value}, from the
+    soft sums of the same one-pass call where the verify's counts come from it (measured 1.40x / 1.41x faster at 3 copies than that
+    call followed by the soft read-out of each copy, profiles/copies_soft_rate.txt), else from ``decoder.decode_soft_frames_u8`` of
+    each copy."""
     from .embed.dct_encoder import DctEncoder
     n, H, W, _ = frames.shape
     n_bits = decoder.bits_per_frame(H, W) if hasattr(decoder, "bits_per_frame") else H * W // 64      # DwtDctSvd(blk=8): H*W//256
@@ -170,17 +222,20 @@ def mark_segment_copies(encoder, decoder, frames, segment_of_frame, num_copies: 
         # one pass for every copy: the frames are read and analyzed once (csrc/copies_kernels.hiph)
         def one_pass(rows_dev, table_dev):
             if hasattr(encoder, "encode_verify_copies_u8") and _reads_like(encoder, decoder):
-                return encoder.encode_verify_copies_u8(frames, rows_dev, table_dev, 8)
+                soft = {"soft": True} if margins else {}
+                return encoder.encode_verify_copies_u8(frames, rows_dev, table_dev, 8, **soft)
             if isinstance(encoder, DctEncoder) and _reads_like(encoder, decoder):
-                return encoder.encode_copies_u8(frames, rows_dev, table_dev, verify_len=8)
+                soft = {"soft": True} if margins else {}
+                return encoder.encode_copies_u8(frames, rows_dev, table_dev, verify_len=8, **soft)
             return encoder.encode_copies_u8(frames, rows_dev, table_dev), None
     return _mark_copies(frames.device, n, H, W, n_bits, segment_of_frame, num_copies, key, min_frequency, one_pass,
                         lambda rows, table: encoder.encode_frames_u8(frames, wm_rows=rows, wm_table=table),
-                        lambda marked: decoder.decode_frames_u8(marked, 8)[0])
+                        lambda marked: decoder.decode_frames_u8(marked, 8)[0],
+                        (lambda marked: decoder.decode_soft_frames_u8(marked, 8)) if margins else None, units_per_frame(decoder, H, W))
 
 
 def mark_segment_copies_yuv420(encoder, decoder, planes, height, width, segment_of_frame, num_copies: int, key=0,
-                               min_frequency: float = 0.5, layout="i420"):
+                               min_frequency: float = 0.5, layout="i420", margins: bool = False):
     """mark_segment_copies on 4:2:0 planes, what a video decoder hands over and an encoder takes: planes is CUDA uint8
     [n, 1.5*H*W] (``layout``: "i420" or "nv12"), the encoder / decoder offer ``encode_planes_yuv420`` /
     ``decode_planes_yuv420``.  Returns (copies, sidecars) with the same sidecar dicts; copies[c] are marked planes of the same
@@ -188,19 +243,23 @@ def mark_segment_copies_yuv420(encoder, decoder, planes, height, width, segment_
     (csrc/planar_copies_kernels.hiph) and copies[c] are views of one [C, n, 1.5*H*W] tensor; a DwtDctSvdEncoder whose decoder
     reads with the same channel-1 scale and blk also hands over the verify's counts
     (``encode_verify_copies_planes_yuv420``).  Otherwise one ``encode_planes_yuv420`` call per copy.  Copies and sidecars are
-    the same either way."""
+    the same either way.  ``margins=True``: "segment_margins" as mark_segment_copies, the soft sums from the DwtDctSvd one-pass
+    call where the verify's counts come from it (1.27x at 3 copies), else from ``decoder.decode_soft_planes_yuv420`` of each copy (always so for the DCT codec)."""
     n = planes.shape[0]
     n_bits = decoder.bits_per_frame(height, width) if hasattr(decoder, "bits_per_frame") else height * width // 64
     one_pass = None
     if hasattr(encoder, "encode_copies_planes_yuv420"):
         def one_pass(rows_dev, table_dev):
             if hasattr(encoder, "encode_verify_copies_planes_yuv420") and _reads_like(encoder, decoder):
-                return encoder.encode_verify_copies_planes_yuv420(planes, height, width, rows_dev, table_dev, 8, layout=layout)
+                soft = {"soft": True} if margins else {}
+                return encoder.encode_verify_copies_planes_yuv420(planes, height, width, rows_dev, table_dev, 8, layout=layout, **soft)
             return encoder.encode_copies_planes_yuv420(planes, height, width, rows_dev, table_dev, layout=layout), None
     return _mark_copies(planes.device, n, height, width, n_bits, segment_of_frame, num_copies, key, min_frequency, one_pass,
                         lambda rows, table: encoder.encode_planes_yuv420(planes, height, width, wm_rows=rows, wm_table=table,
                                                                          layout=layout),
-                        lambda marked: decoder.decode_planes_yuv420(marked, height, width, 8, layout=layout)[0])
+                        lambda marked: decoder.decode_planes_yuv420(marked, height, width, 8, layout=layout)[0],
+                        (lambda marked: decoder.decode_soft_planes_yuv420(marked, height, width, 8, layout=layout)) if margins else None,
+                        units_per_frame(decoder, height, width))
 
 
 def write_sidecars(directory: str, sidecars: dict) -> list[str]:
