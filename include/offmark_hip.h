@@ -354,6 +354,47 @@ int ofmk_svd_embed_copies_soft_rgb8(const uint8_t *in, uint8_t *out, int copies,
 int ofmk_svd_embed_copies_soft_yuv420(const uint8_t *in, uint8_t *out, int layout, int copies, int n, int H, int W,
                                       const uint8_t *wm, int n_wm, const int32_t *wm_rows, const double *scales, int blk,
                                       int L, int32_t *counts, uint8_t *bits, long long *soft, void *stream, const ofmk_opts *opts);
+/* ---- the DCT codec's copies on 4:2:0 planes with the verify of every copy in the same pass, hard and soft ----------------------
+ * ofmk_embed_detect_copies_yuv420 is ofmk_embed_copies_yuv420 plus the read-out of every copy from the pixels the mark kernel
+ * still holds, as ofmk_embed_detect_yuv420 does for one copy and ofmk_embed_detect_copies_rgb8 for RGB frames; the _soft_ call
+ * adds the soft read-out (BUILD EXTENSION, see ofmk_detect_soft_rgb8) of every copy from the same records.  Per chunk: one planar
+ * analysis of the input, ONE launch that writes every copy and every copy's block records, and the finalize of each copy's records
+ * (small launches per copy).  A block has only two marked forms whatever `copies` is (watermark bit 0 or 1), so the launch runs
+ * the fused mark + verify body once for the form of copy 0 and once more for the other form where some copy of the block takes it,
+ * and stores each form into every copy that takes it (csrc/planar_copies_kernels.hiph).  No written copy is read back:
+ * 3 + 1.5 * copies bytes per pixel instead of 3 + 3 * copies for ofmk_embed_copies_yuv420 followed by ofmk_detect_yuv420 of each
+ * copy (3 + 4.5 * copies with ofmk_detect_soft_yuv420 of each copy as well).
+ *   in, layout, copies, wm, n_wm, wm_rows, alpha   as ofmk_embed_copies_yuv420
+ *   out      device u8 [copies][n][1.5*H*W]: byte for byte what ofmk_embed_copies_yuv420 writes; must not overlap `in`
+ *   counts   device int32 [copies][n][L], bits device u8 [copies][n][H*W/64].  For copy c they are what
+ *            ofmk_embed_detect_yuv420(in, ..., wm_rows + c*n, ...) returns -- by that function's contract ofmk_detect_yuv420 of
+ *            out[c] -- integer for integer.  They may hold anything before the call: the fused kernel clears the sums finalize adds
+ *            into (no fill dispatch).  ofmk_embed_detect_copies_yuv420: either may be NULL, not both.
+ *            ofmk_embed_detect_copies_soft_yuv420: both may be NULL (the soft sums alone).
+ *   soft     (the _soft_ call) device int64 [copies][n][L], required: soft[c] == ofmk_detect_soft_yuv420(out[c], layout, alpha),
+ *            integer for integer.  Cleared by the call whatever it held.
+ *   workspace  ofmk_copies_workspace_bytes(frames_in_flight, copies, H, W), as ofmk_embed_detect_copies_rgb8 (every copy keeps its
+ *            own records).  Any workspace >= ofmk_copies_workspace_bytes(1, copies, H, W) is accepted and the call sizes its chunks
+ *            to what fits; a smaller one -- ofmk_workspace_bytes(1, H, W) for instance -- is OFMK_E_WORKSPACE.
+ *   OFMK_F_SEPARATE_DETECT runs the literal sequence instead -- the non-fused planar copies mark, then planar analyze + finalize
+ *   (hard, and soft for the _soft_ call) of each written copy -- with the same results.  Launches are timed as kind 5 (planar
+ *   analyze: of the input once per chunk; the separate route's of each copy), 6 (the fused launch, once per chunk; the separate
+ *   route's mark) and 1 (finalize: per copy and chunk, twice where hard and soft outputs are both asked for).
+ *   With copies == 1 the call equals ofmk_embed_detect_yuv420 (plus ofmk_detect_soft_yuv420 of its output); no result depends on
+ *   chunk_frames, the workspace size or OFMK_F_SEPARATE_DETECT.  Arguments are checked before any HIP call (OFMK_E_ARG): as
+ *   ofmk_embed_copies_yuv420 (layout, H and W multiples of 8, 8-byte aligned buffers, copies in 1..16, out not overlapping in), plus
+ *   L >= 1, the non-NULL outputs above and the opts.  The calls only enqueue (no allocation, no synchronisation), so they capture
+ *   into a hipGraph. */
+int ofmk_embed_detect_copies_yuv420(const uint8_t *in, uint8_t *out, int layout, int copies, int n, int H, int W,
+                                    const uint8_t *wm, int n_wm, const int32_t *wm_rows, double alpha,
+                                    int L, int32_t *counts, uint8_t *bits,
+                                    int chunk_frames, void *workspace, size_t workspace_bytes, void *stream,
+                                    const ofmk_opts *opts);
+int ofmk_embed_detect_copies_soft_yuv420(const uint8_t *in, uint8_t *out, int layout, int copies, int n, int H, int W,
+                                         const uint8_t *wm, int n_wm, const int32_t *wm_rows, double alpha,
+                                         int L, int32_t *counts, uint8_t *bits, long long *soft,
+                                         int chunk_frames, void *workspace, size_t workspace_bytes, void *stream,
+                                         const ofmk_opts *opts);
 int ofmk_yuv420_to_rgb8(const uint8_t *yuv, uint8_t *rgb, int layout, int n, int H, int W, void *stream,
                         const ofmk_opts *opts);
 int ofmk_rgb8_to_yuv420(const uint8_t *rgb, uint8_t *yuv, int layout, int n, int H, int W, void *stream,

@@ -982,6 +982,35 @@ int launch_mark_copies_yuv420(const uint8_t *in, uint8_t *out, int layout, int c
     return OFMK_OK;
 }
 
+// launch_mark_verify_copies_rgb8 on planes (planar_copies_kernels.hiph: mark_verify_copies_yuv420_kernel): every copy of frames
+// [f0, f0+cf) and every copy's records in one launch, after launch_analyze_yuv420 left the input's records in ws.base.  The grid
+// is grid_2d's: its x extent is the tile count emit_block files the per-tile sums under, and it is ws.base.tiles (both are
+// ceil(nblk / kThreads)), which is what fin_base hands finalize.
+int launch_mark_verify_copies_yuv420(const uint8_t *in, uint8_t *out, int layout, int copies, int n, int f0, int cf, int H, int W,
+                                     const uint8_t *wm, int n_wm, const int32_t *wm_rows, double alpha, int L, int32_t *zero_counts,
+                                     const CopiesWorkspace &ws, const Ctx &cx) {
+    const PGeom g = make_pgeom(layout, H, W, ws.base.plane);
+    const MarkArgs m = mark_args(ws.base, H, W, wm, n_wm, nullptr, alpha);
+    const CopyArgs k = make_copy_args(copies, n, f0, wm_rows, g.frame_stride, (size_t)L, (size_t)m.N);
+    const dim3 grid = grid_2d(g.nblk, cf);
+    if ((int)grid.x != ws.base.tiles) return fail(OFMK_E_ARG, "internal: tile count of the launch and of the workspace differ%s");
+    CopyRecs v;
+    v.rec = ws.rec;
+    v.ysum = ws.ysum;
+    v.plane = ws.plane;
+    v.rec_stride = (size_t)ws.base.frames * g.nblk;
+    v.ysum_stride = (size_t)ws.base.frames * ws.base.tiles;
+    v.zero_counts = zero_counts ? zero_counts + (size_t)f0 * L : nullptr;
+    v.L = L;
+    const size_t fo = (size_t)f0 * g.frame_stride;
+    ScopedTiming timing(KIND_PLANAR_MARK, cx);
+    with_fmt(layout, [&](auto fmt) {
+        OFMK_TIMED_LAUNCH(timing, mark_verify_copies_yuv420_kernel<decltype(fmt)::value>, grid, dim3(kThreads), 0, cx.s, in + fo, out + fo, g, m, k, v);
+    });
+    HIP_TRY(hipGetLastError());
+    return OFMK_OK;
+}
+
 // blk = 4 on planes: every copy from one launch per kMaxChunk frames, as launch_svd_copies_rgb8 (H and W multiples of 8: no fringe).
 // soft: as launch_svd_copies_rgb8 (svd_copies_soft_yuv420_kernel).
 int launch_svd_copies_yuv420(const uint8_t *in, uint8_t *out, int layout, int copies, int n, int H, int W, const int32_t *wm_rows,
@@ -1026,6 +1055,63 @@ int svd_copies_soft(uint8_t *out, size_t frame_bytes, int copies, int n, int H, 
         bs.bits = nullptr;
         bs.partial = 0;
         return soft_of(out_q, bs);
+    });
+}
+
+// analyze + the soft finalize of frames [f0, f0+cf) of planar `in` ([n] frames; soft: their [n][L] sums, cleared by the caller)
+int detect_soft_chunk_yuv420(const uint8_t *in, int layout, int f0, int cf, int H, int W, int L, double alpha, long long *soft,
+                             const Workspace &ws, const Ctx &cx) {
+    if (int rc = launch_analyze_yuv420(in + (size_t)f0 * H * W * 3 / 2, layout, cf, H, W, ws, cx)) return rc;
+    FinArgs a = fin_base(ws, H, W, alpha);
+    a.L = L;
+    a.soft = soft + (size_t)f0 * L;
+    return launch_finalize(a, cf, cx);
+}
+
+// The host half of ofmk_embed_detect_copies_yuv420 and ofmk_embed_detect_copies_soft_yuv420 (want_soft: the second; its counts and
+// bits are optional and soft is required, the first needs counts or bits and has no soft).
+int embed_detect_copies_yuv420(const uint8_t *in, uint8_t *out, int layout, int copies, int n, int H, int W, const uint8_t *wm, int n_wm,
+                               const int32_t *wm_rows, double alpha, int L, int32_t *counts, uint8_t *bits, long long *soft,
+                               bool want_soft, int chunk_frames, void *workspace, size_t workspace_bytes, void *stream,
+                               const ofmk_opts *opts) {
+    if (int orc = check_opts(opts)) return orc;
+    int rc = check_embed_args(in, out, n, H, W, wm, n_wm);
+    if (rc) return rc;
+    if ((rc = check_planar(layout, H, W, in, out))) return rc;
+    const size_t fs = (size_t)H * W * 3 / 2;
+    if ((rc = check_copies(in, out, copies, n, fs))) return rc;
+    if ((rc = want_soft ? check_soft_args(out, n, H, W, L, soft) : check_detect_args(out, n, H, W, L, counts, bits))) return rc;
+    CopiesWorkspace ws;
+    if ((rc = carve_copies(workspace, workspace_bytes, copies, H, W, chunk_frames, ws))) return rc;
+    const Ctx cx = make_ctx(stream, opts);
+    const bool hard = counts || bits;
+    const size_t N = (size_t)((long long)H * W / 64);
+    if (soft) HIP_TRY(launch_zero(soft, (size_t)copies * n * L * sizeof(long long), cx.s));
+    return for_chunks(n, ws.base.frames, [&](int f0, int cf) {      // one analysis of the input per chunk serves every copy
+        if (int rc = launch_analyze_yuv420(in + (size_t)f0 * fs, layout, cf, H, W, ws.base, cx)) return rc;
+        if (!(cx.flags & OFMK_F_SEPARATE_DETECT)) {
+            if (int rc = launch_mark_verify_copies_yuv420(in, out, layout, copies, n, f0, cf, H, W, wm, n_wm, wm_rows, alpha, L, counts, ws, cx))
+                return rc;
+            for (int q = 0; q < copies; ++q) {                    // the small launches per copy on the records the fused launch left
+                if (hard)
+                    if (int rc = finalize_detect_copy(q, n, f0, cf, H, W, L, alpha, counts, bits, ws, cx)) return rc;
+                if (soft)
+                    if (int rc = finalize_soft_copy(q, n, f0, cf, H, W, L, alpha, soft, ws, cx)) return rc;
+            }
+            return (int)OFMK_OK;
+        }
+        // the literal sequence: mark every copy, then detect (and soft-detect) each written copy (its analysis overwrites the
+        // input's records, which the chunk's mark launch, earlier in the stream, has already used)
+        if (int rc = launch_mark_copies_yuv420(in, out, layout, copies, n, f0, cf, H, W, wm, n_wm, wm_rows, alpha, ws.base, cx)) return rc;
+        for (int q = 0; q < copies; ++q) {
+            const uint8_t *out_q = out + (size_t)q * n * fs;
+            if (hard)
+                if (int rc = detect_chunk_yuv420(out_q, layout, f0, cf, H, W, L, alpha, counts ? counts + (size_t)q * n * L : nullptr,
+                                                 bits ? bits + (size_t)q * n * N : nullptr, ws.base, cx)) return rc;
+            if (soft)
+                if (int rc = detect_soft_chunk_yuv420(out_q, layout, f0, cf, H, W, L, alpha, soft + (size_t)q * n * L, ws.base, cx)) return rc;
+        }
+        return (int)OFMK_OK;
     });
 }
 
@@ -1575,6 +1661,21 @@ int ofmk_embed_copies_yuv420(const uint8_t *in, uint8_t *out, int layout, int co
         if (int rc = launch_analyze_yuv420(in + (size_t)f0 * H * W * 3 / 2, layout, cf, H, W, ws, cx)) return rc;
         return launch_mark_copies_yuv420(in, out, layout, copies, n, f0, cf, H, W, wm, n_wm, wm_rows, alpha, ws, cx);
     });
+}
+
+int ofmk_embed_detect_copies_yuv420(const uint8_t *in, uint8_t *out, int layout, int copies, int n, int H, int W, const uint8_t *wm,
+                                    int n_wm, const int32_t *wm_rows, double alpha, int L, int32_t *counts, uint8_t *bits,
+                                    int chunk_frames, void *workspace, size_t workspace_bytes, void *stream, const ofmk_opts *opts) {
+    return embed_detect_copies_yuv420(in, out, layout, copies, n, H, W, wm, n_wm, wm_rows, alpha, L, counts, bits, nullptr, false,
+                                      chunk_frames, workspace, workspace_bytes, stream, opts);
+}
+
+int ofmk_embed_detect_copies_soft_yuv420(const uint8_t *in, uint8_t *out, int layout, int copies, int n, int H, int W, const uint8_t *wm,
+                                         int n_wm, const int32_t *wm_rows, double alpha, int L, int32_t *counts, uint8_t *bits,
+                                         long long *soft, int chunk_frames, void *workspace, size_t workspace_bytes, void *stream,
+                                         const ofmk_opts *opts) {
+    return embed_detect_copies_yuv420(in, out, layout, copies, n, H, W, wm, n_wm, wm_rows, alpha, L, counts, bits, soft, true,
+                                      chunk_frames, workspace, workspace_bytes, stream, opts);
 }
 
 int ofmk_svd_embed_copies_yuv420(const uint8_t *in, uint8_t *out, int layout, int copies, int n, int H, int W, const uint8_t *wm,

@@ -84,6 +84,10 @@ SIGNATURES = {
                                             _vp, _op]),
     "ofmk_svd_embed_copies_soft_yuv420": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _dp, _i32, _i32, _vp, _vp,
                                                  _vp, _vp, _op]),
+    "ofmk_embed_detect_copies_yuv420": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _f64, _i32, _vp, _vp, _i32, _vp,
+                                               _sz, _vp, _op]),
+    "ofmk_embed_detect_copies_soft_yuv420": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _f64, _i32, _vp, _vp, _vp, _i32,
+                                                    _vp, _sz, _vp, _op]),
     "ofmk_yuv420_to_rgb8": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _op]),
     "ofmk_rgb8_to_yuv420": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _op]),
     "ofmk_probe_xcc": (_i32, [_vp, _i32, _vp, _op]),

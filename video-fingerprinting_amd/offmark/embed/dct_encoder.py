@@ -107,8 +107,21 @@ class DctEncoder:
         wm = wm_table if wm_table is not None else self._device_wm(height * width // 64)
         return self.engine.embed_yuv420(planes, height, width, wm, alpha=self.alpha, wm_row=wm_rows, out=out, layout=layout)
 
-    def encode_copies_planes_yuv420(self, planes, height, width, wm_rows, wm_table, out=None, layout="i420"):
+    def encode_copies_planes_yuv420(self, planes, height, width, wm_rows, wm_table, out=None, layout="i420", verify_len=None, soft=False):
         """planes: CUDA uint8 [n, 1.5*H*W]; wm_rows: [C, n] rows of ``wm_table`` per copy and frame.  Returns the C marked copies
         [C, n, 1.5*H*W] in one pass (the planes are read, analyzed and converted once); copy c equals
-        encode_planes_yuv420(planes, height, width, wm_rows=wm_rows[c], wm_table=wm_table) byte for byte."""
-        return self.engine.embed_copies_yuv420(planes, height, width, wm_table, wm_rows, alpha=self.alpha, out=out, layout=layout)
+        encode_planes_yuv420(planes, height, width, wm_rows=wm_rows[c], wm_table=wm_table) byte for byte.  With ``verify_len`` (a
+        payload length): returns (copies, counts int32 [C, n, verify_len]), counts[c] being what a DctDecoder with this alpha reads
+        from copy c (decode_planes_yuv420), taken in the same pass.  With ``soft=True`` as well: (copies, counts, soft int64
+        [C, n, verify_len]), soft[c] being that decoder's decode_soft_planes_yuv420 of copy c, from the same pass."""
+        if verify_len is None:
+            if soft:
+                raise ValueError("soft=True needs verify_len (the payload length)")
+            return self.engine.embed_copies_yuv420(planes, height, width, wm_table, wm_rows, alpha=self.alpha, out=out, layout=layout)
+        if soft:
+            copies, counts, _bits, sums = self.engine.embed_detect_copies_yuv420(planes, height, width, wm_table, wm_rows, verify_len,
+                                                                                 alpha=self.alpha, out=out, layout=layout, soft=True)
+            return copies, counts, sums
+        copies, counts, _bits = self.engine.embed_detect_copies_yuv420(planes, height, width, wm_table, wm_rows, verify_len,
+                                                                       alpha=self.alpha, out=out, layout=layout)
+        return copies, counts

@@ -744,6 +744,42 @@ class DctEngine:
                                                      _hip.current_stream(), self._o()))
         return out
 
+    def embed_detect_copies_yuv420(self, planes, H, W, wm, wm_rows, L, alpha=20, out=None, want_bits=False, counts=None, copies=None,
+                                   layout="i420", soft=None):
+        """embed_copies_yuv420 and the verify of every copy in the same pass: returns (out uint8 [C, n, 1.5*H*W], counts int32
+        [C, n, L], bits uint8 [C, n, N] or None).  ``out`` is embed_copies_yuv420's result byte for byte; counts[c] / bits[c] are what
+        ``embed_detect_yuv420(planes, H, W, wm, L, alpha, wm_row=wm_rows[c])`` returns, i.e. ``detect_yuv420(out[c], H, W, L, alpha)``.
+        Each copy is read out from the pixels the mark kernel still holds, so no copy is read back; the kernel runs the fused
+        mark + verify body once per marked form a block needs (at most two), not once per copy (csrc/planar_copies_kernels.hiph).
+        ``soft`` (build extension): True or an int64 [C, n, L] tensor -- also the soft sums of every copy, soft[c] ==
+        ``detect_soft_yuv420(out[c], H, W, L, alpha)``, from the same records; returned as a fourth element."""
+        t = self.torch
+        n = self._check_planar(planes, H, W)
+        fmt = self._layout(layout)
+        N = H * W // 64
+        wm = self._wm(wm, N)
+        rows, C = self._copy_rows(wm_rows, n, wm.shape[0], copies)
+        out = self._out(out, planes, (C, n, H * W * 3 // 2))
+        L = int(L)
+        counts = self._counts(counts, n, L, copies=C)
+        bits = t.empty((C, n, N), dtype=t.uint8, device=self.device) if want_bits else None
+        want_soft = soft is not None and soft is not False
+        if want_soft:
+            soft = self._soft(soft, n, L, copies=C)
+        cf = self._chunk(n, H, W)
+        ws = self.copies_workspace(H, W, cf, C)
+        if want_soft:
+            _hip.check(self.lib.ofmk_embed_detect_copies_soft_yuv420(planes.data_ptr(), out.data_ptr(), fmt, C, n, H, W, wm.data_ptr(),
+                                                                     wm.shape[0], _hip.ptr(rows), float(alpha), L, counts.data_ptr(),
+                                                                     _hip.ptr(bits), soft.data_ptr(), cf, ws.data_ptr(), ws.numel(),
+                                                                     _hip.current_stream(), self._o()))
+            return out, counts, bits, soft
+        _hip.check(self.lib.ofmk_embed_detect_copies_yuv420(planes.data_ptr(), out.data_ptr(), fmt, C, n, H, W, wm.data_ptr(),
+                                                            wm.shape[0], _hip.ptr(rows), float(alpha), L, counts.data_ptr(),
+                                                            _hip.ptr(bits), cf, ws.data_ptr(), ws.numel(), _hip.current_stream(),
+                                                            self._o()))
+        return out, counts, bits
+
     def svd_embed_copies_yuv420(self, planes, H, W, wm, wm_rows, scale=15, scales=None, blk=4, out=None, L=None, want_bits=False,
                                 counts=None, partial=False, copies=None, layout="i420", soft=None):
         """The DwtDctSvd codec's copies on 4:2:0 planes in one pass: copy c of the uint8 [C, n, 1.5*H*W] result equals

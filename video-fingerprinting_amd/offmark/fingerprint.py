@@ -235,7 +235,7 @@ def mark_segment_copies(encoder, decoder, frames, segment_of_frame, num_copies: 
 
 
 def mark_segment_copies_yuv420(encoder, decoder, planes, height, width, segment_of_frame, num_copies: int, key=0,
-                               min_frequency: float = 0.5, layout="i420", margins: bool = False):
+                               min_frequency: float = 0.5, layout="i420", margins: bool = False, one_pass_verify: bool = False):
     """mark_segment_copies on 4:2:0 planes, what a video decoder hands over and an encoder takes: planes is CUDA uint8
     [n, 1.5*H*W] (``layout``: "i420" or "nv12"), the encoder / decoder offer ``encode_planes_yuv420`` /
     ``decode_planes_yuv420``.  Returns (copies, sidecars) with the same sidecar dicts; copies[c] are marked planes of the same
@@ -244,7 +244,15 @@ def mark_segment_copies_yuv420(encoder, decoder, planes, height, width, segment_
     reads with the same channel-1 scale and blk also hands over the verify's counts
     (``encode_verify_copies_planes_yuv420``).  Otherwise one ``encode_planes_yuv420`` call per copy.  Copies and sidecars are
     the same either way.  ``margins=True``: "segment_margins" as mark_segment_copies, the soft sums from the DwtDctSvd one-pass
-    call where the verify's counts come from it (1.27x at 3 copies), else from ``decoder.decode_soft_planes_yuv420`` of each copy (always so for the DCT codec)."""
+    call where the verify's counts come from it (1.27x at 3 copies), else from ``decoder.decode_soft_planes_yuv420`` of each copy (so for the DCT codec
+    by default).
+    ``one_pass_verify=True`` (opt-in; no effect for other encoders or a decoder that reads differently): with a DctEncoder and a
+    DctDecoder of the same alpha the counts -- and with ``margins=True`` the soft sums -- come from the one-pass call
+    (``encode_copies_planes_yuv420(..., verify_len=8[, soft=True])``, csrc/planar_copies_kernels.hiph) and the decoder is not called;
+    copies and sidecars are the same.  Measured at 300 x 1080p against the default route (profiles/planar_copies_verify_rate.txt,
+    C = 2 / 3 / 8): with margins 1.11 / 1.40 / 1.87x faster on I420 and 1.15 / 1.47 / 1.98x on NV12; WITHOUT margins 0.81 / 0.98 / 1.28x
+    and 0.83 / 1.03 / 1.34x -- slower at 2 copies, a tie at 3, faster at 8 -- so the default stays False."""
+    from .embed.dct_encoder import DctEncoder
     n = planes.shape[0]
     n_bits = decoder.bits_per_frame(height, width) if hasattr(decoder, "bits_per_frame") else height * width // 64
     one_pass = None
@@ -253,6 +261,9 @@ def mark_segment_copies_yuv420(encoder, decoder, planes, height, width, segment_
             if hasattr(encoder, "encode_verify_copies_planes_yuv420") and _reads_like(encoder, decoder):
                 soft = {"soft": True} if margins else {}
                 return encoder.encode_verify_copies_planes_yuv420(planes, height, width, rows_dev, table_dev, 8, layout=layout, **soft)
+            if one_pass_verify and isinstance(encoder, DctEncoder) and _reads_like(encoder, decoder):
+                soft = {"soft": True} if margins else {}
+                return encoder.encode_copies_planes_yuv420(planes, height, width, rows_dev, table_dev, layout=layout, verify_len=8, **soft)
             return encoder.encode_copies_planes_yuv420(planes, height, width, rows_dev, table_dev, layout=layout), None
     return _mark_copies(planes.device, n, height, width, n_bits, segment_of_frame, num_copies, key, min_frequency, one_pass,
                         lambda rows, table: encoder.encode_planes_yuv420(planes, height, width, wm_rows=rows, wm_table=table,
