@@ -172,6 +172,36 @@ int ofmk_svd_embed_detect_rgb8(const uint8_t *in, uint8_t *out, int n, int H, in
  * everywhere. */
 int ofmk_svd_detect_soft_rgb8(const uint8_t *in, int n, int H, int W, int L, const double *scales, int blk,
                               long long *soft, void *stream, const ofmk_opts *opts);
+/* ---- block-grid resync: reading CROPPED frames (BUILD EXTENSION, not reference semantics) ---------------------------------
+ * A crop moves the phase of the 8x8 unit grid (64 possibilities) and changes the frame's block count, which scrambles the
+ * position rule (unit index mod L).  DwtDctSvd has no frame-global dependency: a unit's read-out depends on its own 8x8 pixels
+ * only, so at the right phase a cropped frame's units are bit for bit the marked frame's.  Two calls, both for blk 4, YUV
+ * channel 1 and interleaved u8 RGB frames of any H, W >= 8 (no multiple of 8 needed):
+ *
+ * ofmk_svd_sync_scores_rgb8: the dense phase search.
+ *   scores   device int64 [n][64]; scores[f][8*py + px] = sum of |m| over the full 8x8 windows of frame f with top-left pixel
+ *            (py + 8i, px + 8j), i < (H - py) / 8, j < (W - px) / 8; m is exactly the unit metric of ofmk_svd_detect_soft_rgb8
+ *            (blk 4) on that window.  A phase without a full window scores 0.  Cleared by the call whatever it held.
+ *            Divided by 2^14 * windows, a marked grid scores near 1 and any other grid (or unmarked content) near 0.7; flat
+ *            content carries no phase information (offmark.resync.best_phase).
+ *   One frame read and one solver run per pixel origin, instead of 64 read-outs of 64 shifted copies.
+ *   OFMK_E_ARG before any HIP call: null pointers, n <= 0, H or W < 8, H*W >= 2^28, blk != 4, a nan / inf scale, a positive scale
+ *   below 1e-3, scales[1] <= 0, unknown flag bits.
+ *
+ * ofmk_svd_detect_soft_window_rgb8: the soft read-out of the units at phase (py, px), with the positions of a wider canvas.
+ *   py, px        0..7; unit (i, j) is the 8x8 block at pixel (py + 8i, px + 8j), rows = (H - py) / 8, cols = (W - px) / 8 units;
+ *                 read through the frame's own pitch (no copy of the window)
+ *   canvas_cols   units per row of the frame the positions refer to (the uncropped frame's W / 8); >= cols
+ *   base          >= 0; unit (i, j) is added into position (base + i*canvas_cols + j) mod L; base + rows*canvas_cols < 2^31
+ *   soft          device int64 [n][L], cleared by the call; scales[1] <= 0: all zeros
+ *   With py = px = 0, canvas_cols = W / 8, base = 0 and H, W multiples of 8 this is ofmk_svd_detect_soft_rgb8, integer for
+ *   integer.  OFMK_E_ARG: the soft call's checks, a phase outside 0..7, no full unit, canvas_cols < cols, base < 0, the 2^31
+ *   bound, blk != 4.
+ * Both are graph capturable and timed as kind 4 (svd); OFMK_F_PARTIAL_COUNTS and the tile-order flags are ignored. */
+int ofmk_svd_sync_scores_rgb8(const uint8_t *in, int n, int H, int W, const double *scales, int blk, long long *scores,
+                              void *stream, const ofmk_opts *opts);
+int ofmk_svd_detect_soft_window_rgb8(const uint8_t *in, int n, int H, int W, int py, int px, int canvas_cols, int base, int L,
+                                     const double *scales, int blk, long long *soft, void *stream, const ofmk_opts *opts);
 /* ---- C differently marked copies of the same frames in one pass (the A/B workflow) ----------------------------------
  * tests/mark_video_to_hls.py:331-342 decodes every segment once per copy and marks it with payload segment(4b)||copy(4b).
  * These calls read the frames once, do the part of the codec that does not depend on the watermark bit once (DCT: analyze's

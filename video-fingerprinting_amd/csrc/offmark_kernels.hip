@@ -47,6 +47,7 @@
 #include "svd_planar_kernels.hiph"
 #include "copies_kernels.hiph"
 #include "planar_copies_kernels.hiph"
+#include "resync_kernels.hiph"
 
 namespace {
 
@@ -900,6 +901,16 @@ int svd_detect_soft(int n, int H, int W, int L, const double *scales, long long 
     return OFMK_OK;
 }
 
+// ---- block-grid resync of cropped frames (resync_kernels.hiph; blk 4, channel 1, RGB) -------------------------------------------
+// The checks the two resync calls share on top of their own: blk 4 only, finite scales, and -- need_mark -- a marked channel 1.
+int check_resync_scales(SvdArgs &a, const double *scales, int blk, bool need_mark) {
+    if (blk != 4) return fail(OFMK_E_ARG, "the resync calls are for blk 4%s");
+    memset(&a, 0, sizeof(a));
+    if (int rc = set_scales(a, scales, true)) return rc;
+    if (need_mark && !(a.scales[1] > 0.f)) return fail(OFMK_E_ARG, "scales[1] must be positive: the phase search reads channel 1%s");
+    return OFMK_OK;
+}
+
 // ---- C marked copies of the same frames (copies_kernels.hiph) -------------------------------------------------------
 constexpr int kMaxCopies = 16;       // a payload's copy field has 4 bits (fingerprint.payload_for_segment)
 
@@ -1291,6 +1302,70 @@ int ofmk_svd_detect_soft_rgb8(const uint8_t *in, int n, int H, int W, int L, con
     return svd_detect_soft(n, H, W, L, scales, soft, stream, [&](const SvdArgs &a) {
         return launch_svd_rgb8(in, nullptr, n, H, W, SVD_DETECT_SOFT, blk, a, make_ctx(stream, opts));
     });
+}
+
+// Build extension, not reference semantics (resync_kernels.hiph): scores[f][8 py + px] = sum of |svd_soft_metric| over the full 8x8
+// windows of frame f at grid phase (py, px); int64 [n][64], cleared here whatever it held.  H, W: any values >= 8.
+int ofmk_svd_sync_scores_rgb8(const uint8_t *in, int n, int H, int W, const double *scales, int blk, long long *scores, void *stream,
+                              const ofmk_opts *opts) {
+    if (int orc = check_opts(opts)) return orc;
+    if (int rc = check_dims(n, H, W)) return rc;
+    if (!in || !scores) return fail(OFMK_E_ARG, "null pointer%s");
+    SvdArgs a;
+    if (int rc = check_resync_scales(a, scales, blk, true)) return rc;
+    const Ctx cx = make_ctx(stream, opts);
+    HIP_TRY(launch_zero(scores, (size_t)n * 64 * sizeof(long long), cx.s));
+    SyncGeom g;
+    g.H = H;
+    g.W = W;
+    g.rects_x = (W - 7 + kSyncRect * kSyncStrip - 1) / (kSyncRect * kSyncStrip);
+    g.rects = g.rects_x * ((H - 7 + kSyncRect - 1) / kSyncRect);
+    g.frame_stride = (size_t)H * W * 3;
+    g.scale = a.scales[1];
+    for_chunks(n, kMaxChunk, [&](int f0, int cf) {
+        ScopedTiming timing(KIND_SVD, cx);
+        OFMK_TIMED_LAUNCH(timing, svd_sync_scores_rgb8_kernel, dim3((unsigned)g.rects, (unsigned)cf), dim3(kThreads), 0, cx.s,
+                          in + (size_t)f0 * g.frame_stride, g, reinterpret_cast<unsigned long long *>(scores) + (size_t)f0 * 64);
+        return OFMK_OK;
+    });
+    HIP_TRY(hipGetLastError());
+    return OFMK_OK;
+}
+
+// Build extension, not reference semantics (resync_kernels.hiph): the soft read-out of the units at grid phase (py, px) -- unit (i, j)
+// is the 8x8 block at pixel (py + 8i, px + 8j) -- added into position (base + i * canvas_cols + j) mod L; int64 [n][L], cleared here.
+// py = px = 0, canvas_cols = W / 8, base = 0 on frames with H, W multiples of 8: ofmk_svd_detect_soft_rgb8, integer for integer.
+// scales[1] <= 0: all zeros, as that call.
+int ofmk_svd_detect_soft_window_rgb8(const uint8_t *in, int n, int H, int W, int py, int px, int canvas_cols, int base, int L,
+                                     const double *scales, int blk, long long *soft, void *stream, const ofmk_opts *opts) {
+    if (int orc = check_opts(opts)) return orc;
+    if (int rc = check_soft_args(in, n, H, W, L, soft)) return rc;
+    if (py < 0 || py > 7 || px < 0 || px > 7) return fail(OFMK_E_ARG, "the phase (py, px) must be in 0..7%s");
+    const int rows = (H - py) / 8, cols = (W - px) / 8;
+    if (rows < 1 || cols < 1) return fail(OFMK_E_ARG, "no full 8x8 unit at this phase%s");
+    if (canvas_cols < cols) return fail(OFMK_E_ARG, "canvas_cols is smaller than the window's units per row%s");
+    if (base < 0) return fail(OFMK_E_ARG, "base must not be negative%s");
+    if ((long long)base + (long long)rows * canvas_cols >= (1LL << 31)) return fail(OFMK_E_ARG, "base + rows * canvas_cols must be < 2^31%s");
+    SvdArgs sa;
+    if (int rc = check_resync_scales(sa, scales, blk, false)) return rc;
+    const Ctx cx = make_ctx(stream, opts);
+    HIP_TRY(launch_zero(soft, (size_t)n * L * sizeof(long long), cx.s));
+    if (!(sa.scales[1] > 0.f)) return OFMK_OK;
+    Geom g = svd_geom(H, W);                 // the frame's W and stride ...
+    g.wb = cols;                             // ... with the window's units
+    g.inv_wb = 1.0f / (float)cols;
+    g.nblk = rows * cols;
+    for_chunks(n, kMaxChunk, [&](int f0, int cf) {
+        ScopedTiming timing(KIND_SVD, cx);
+        Geom gc = g;
+        gc.frames = cf;
+        const WindowArgs w{py, px, canvas_cols, base, L, sa.scales[1], soft + (size_t)f0 * L};
+        OFMK_TIMED_LAUNCH(timing, svd_soft_window_rgb8_kernel, xcd_grid(g.nblk, cf), dim3(kThreads), 0, cx.s,
+                          in + (size_t)f0 * g.frame_stride, gc, w);
+        return OFMK_OK;
+    });
+    HIP_TRY(hipGetLastError());
+    return OFMK_OK;
 }
 
 int ofmk_svd_embed_detect_rgb8(const uint8_t *in, uint8_t *out, int n, int H, int W, const uint8_t *wm, int n_wm,

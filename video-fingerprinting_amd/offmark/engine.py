@@ -544,6 +544,29 @@ class DctEngine:
                                                       soft.data_ptr(), _hip.current_stream(), self._o()))
         return soft
 
+    # -- block-grid resync of cropped frames (build extension, not reference semantics; blk 4, channel 1; offmark.resync) --------
+    def svd_sync_scores(self, frames, scale=15, scales=None, blk=4, scores=None):
+        """The dense phase search: int64 [n, 64], entry 8 * py + px = the sum of |unit metric| (svd_detect_soft's, blk 4) over the
+        full 8x8 windows of the frame at grid phase (py, px).  H and W are any values >= 8.  offmark.resync.best_phase reads it."""
+        t = self.torch
+        n, H, W = self._check_frames(frames, t.uint8)
+        scores = self._soft(scores, n, 64)
+        _hip.check(self.lib.ofmk_svd_sync_scores_rgb8(frames.data_ptr(), n, H, W, _hip.scales3(scale, scales), int(blk), scores.data_ptr(),
+                                                      _hip.current_stream(), self._o()))
+        return scores
+
+    def svd_detect_soft_window(self, frames, L, phase, canvas_cols, base=0, scale=15, scales=None, blk=4, soft=None):
+        """svd_detect_soft of the units at grid ``phase`` = (py, px): unit (i, j) is the 8x8 block at pixel (py + 8i, px + 8j) and
+        adds into position (base + i * canvas_cols + j) % L, the position it has in a frame ``canvas_cols`` units wide.  int64 [n, L]."""
+        t = self.torch
+        n, H, W = self._check_frames(frames, t.uint8)
+        soft = self._soft(soft, n, L)
+        py, px = phase
+        _hip.check(self.lib.ofmk_svd_detect_soft_window_rgb8(frames.data_ptr(), n, H, W, int(py), int(px), int(canvas_cols), int(base), int(L),
+                                                             _hip.scales3(scale, scales), int(blk), soft.data_ptr(), _hip.current_stream(),
+                                                             self._o()))
+        return soft
+
     def svd_embed_detect(self, frames, wm, L, scale=15, wm_row=None, out=None, want_bits=False, scales=None, blk=4, counts=None,
                          partial=False):
         t = self.torch

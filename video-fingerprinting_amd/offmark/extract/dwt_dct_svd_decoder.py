@@ -50,6 +50,17 @@ class DwtDctSvdDecoder:
         """frames: CUDA uint8 [n, H, W, 3] -> soft sums int64 [n, L] on device (> 0 reads as 1)."""
         return self.engine.svd_detect_soft(frames, payload_len, scales=self._scales, blk=self.blk)
 
+    # -- block-grid resync of cropped frames (build extension; blk 4 only: offmark.resync) ---------------------------------------
+    def sync_scores_u8(self, frames):
+        """frames: CUDA uint8 [n, H, W, 3], any H, W >= 8 -> int64 [n, 64] on device: per grid phase 8 * py + px the sum of
+        |unit metric| over the phase's full 8x8 windows (engine.svd_sync_scores)."""
+        return self.engine.svd_sync_scores(frames, scales=self._scales, blk=self.blk)
+
+    def decode_soft_window_u8(self, frames, L, phase, canvas_cols, base=0):
+        """The soft sums int64 [n, L] of the units at grid ``phase``, with the positions of a frame ``canvas_cols`` units wide
+        (engine.svd_detect_soft_window)."""
+        return self.engine.svd_detect_soft_window(frames, L, phase, canvas_cols, base=base, scales=self._scales, blk=self.blk)
+
     def decode_soft_planes_yuv420(self, planes, height, width, payload_len, layout="i420"):
         """planes: CUDA uint8 [n, 1.5*H*W] (I420 or NV12) -> soft sums int64 [n, L] on device."""
         return self.engine.svd_detect_soft_yuv420(planes, height, width, payload_len, scales=self._scales, blk=self.blk, layout=layout)

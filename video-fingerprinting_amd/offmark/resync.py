@@ -1,0 +1,116 @@
+"""Reading CROPPED leaks with the DwtDctSvd codec: block-grid resync (host side, NumPy only).
+
+Build extension, not reference semantics.  A crop does two mechanical things to a block-transform mark:
+  * it moves the PHASE of the 8x8 unit grid (64 possibilities), and
+  * it changes the frame's block count, so the position rule (unit index mod L) scrambles the payload positions.
+DwtDctSvd (blk 4) has no frame-global dependency: a unit's read-out depends on its own 8x8 pixels only.  At the right phase a
+cropped leak's units are therefore exactly the marked frame's units, and both effects can be undone:
+  1. ``DwtDctSvdDecoder.sync_scores_u8`` gives, per phase, the sum of |soft metric| over the phase's units; on the marked grid
+     every unit sits at +-2^14, on any other grid (and on unmarked content) the mean is near 0.7 * 2^14: ``best_phase``.
+  2. ``DwtDctSvdDecoder.decode_soft_window_u8`` reads the units of that phase with the positions of the UNCROPPED frame's width
+     (``canvas_cols``); what is then unknown is one rotation of the L positions -- the crop's whole units above and left of the
+     leak -- common to every frame of the leak: ``align_segments`` resolves it against the publisher's own candidate payloads.
+``read_cropped_leak`` is the recipe end to end.  Rescaled leaks are a different problem (resampling) and not handled.
+"""
+from __future__ import annotations
+
+import numpy as np
+
+ONE = 16384      # the soft metric's fixed point (2^14)
+
+
+def units_per_phase(H: int, W: int) -> np.ndarray:
+    """int64 [64]: full 8x8 units of an H x W frame at phase (py, px), at index 8 * py + px; 0 where none fits."""
+    r = np.maximum((H - np.arange(8)) // 8, 0).astype(np.int64)
+    c = np.maximum((W - np.arange(8)) // 8, 0).astype(np.int64)
+    return (r[:, None] * c[None, :]).reshape(64)
+
+
+def best_phase(scores, H: int, W: int) -> dict:
+    """scores: [64] or [n, 64] sums of |soft metric| per phase (rows are added) of H x W frames ->
+    dict(phase=(py, px), normalised=float64 [64], contrast=top / second).  normalised = score / (2^14 * units * frames): about 1
+    on the marked grid; phases without units are excluded (0 there).  No verdict: the caller judges ``contrast``, which is about
+    1.0 on flat content (a flat frame carries no phase information) and inf when one phase at most has units or the
+    second-best scores 0."""
+    s = np.asarray(scores, dtype=np.int64).reshape(-1, 64)
+    units = units_per_phase(H, W)
+    have = units > 0
+    if not have.any():
+        raise ValueError(f"a {H}x{W} frame holds no 8x8 unit")
+    norm = np.zeros(64, np.float64)
+    norm[have] = s.sum(axis=0)[have] / (float(ONE) * units[have] * s.shape[0])
+    order = np.argsort(-np.where(have, norm, -1.0), kind="stable")
+    top = int(order[0])
+    second = float(norm[order[1]]) if have.sum() > 1 else 0.0
+    contrast = float(norm[top] / second) if second > 0 else float("inf")
+    return dict(phase=(top // 8, top % 8), normalised=norm, contrast=contrast)
+
+
+def shuffled(payload, key) -> np.ndarray:
+    """The payload as the marked frames carry it at positions 0..L-1: Shuffler(key)'s permutation."""
+    from .generator.shuffler import Shuffler
+    p = np.asarray(payload).reshape(-1)
+    return np.asarray(Shuffler(key=key).generate_wm(p, (p.size,))).reshape(-1)
+
+
+def align_segments(soft_by_segment, candidates, key) -> dict:
+    """One rotation of the L payload positions, common to all segments, and per segment the candidate it then reads as.
+    soft_by_segment: [S, L] soft sums read with base 0; candidates[s]: the payloads (L bits each) segment s may carry.
+    With T[s][q] = soft[s][(q - base) % L], maximises over base in 0..L-1
+        sum_s max_k sum_q (2 * shuffled(candidates[s][k])[q] - 1) * T[s][q]
+    (integers, so ties are exact).  -> dict(base, picks int [S] (index into candidates[s]; the first on a tie), score,
+    runner_up_score (the best other base's), ambiguous (another base, or another candidate of a segment at the best base, scores
+    the same))."""
+    soft = np.asarray(soft_by_segment, dtype=np.int64)
+    if soft.ndim != 2 or len(candidates) != soft.shape[0]:
+        raise ValueError("soft_by_segment must be [S, L] with one candidate list per segment")
+    S, L = soft.shape
+    signs = []
+    for s in range(S):
+        c = np.stack([2 * shuffled(p, key).astype(np.int64) - 1 for p in candidates[s]])
+        if c.shape[1] != L:
+            raise ValueError(f"candidates of segment {s} are not {L} bits long")
+        signs.append(c)
+    totals = np.empty(L, np.int64)
+    picks = np.empty((L, S), np.int64)
+    tied_pick = np.zeros(L, bool)
+    for base in range(L):
+        T = np.roll(soft, base, axis=1)                    # T[s][q] = soft[s][(q - base) % L]
+        total = 0
+        for s in range(S):
+            corr = signs[s] @ T[s]
+            k = int(np.argmax(corr))
+            picks[base, s] = k
+            tied_pick[base] |= int((corr == corr[k]).sum()) > 1
+            total += int(corr[k])
+        totals[base] = total
+    best = int(np.argmax(totals))
+    others = np.delete(totals, best)
+    runner_up = int(others.max()) if others.size else None
+    ambiguous = bool(tied_pick[best] or (runner_up is not None and runner_up == int(totals[best])))
+    return dict(base=best, picks=picks[best].copy(), score=int(totals[best]), runner_up_score=runner_up, ambiguous=ambiguous)
+
+
+def _host(x) -> np.ndarray:
+    return np.asarray(x.cpu() if hasattr(x, "cpu") else x)
+
+
+def read_cropped_leak(decoder, frames, segment_of_frame, canvas_width: int, candidates, key=0, L: int = 8, search_frames: int = 8) -> dict:
+    """A cropped leak's copy per segment.  decoder: a DwtDctSvdDecoder (blk 4); frames: CUDA uint8 [n, H, W, 3], the leak as it is
+    (any H, W >= 8); segment_of_frame: [n] segment label per frame; canvas_width: the marked (uncropped) frames' width in pixels;
+    candidates: per segment, in the order of the sorted distinct labels (or a dict keyed by label), the payloads it may carry.
+    Phase search on the first ``search_frames`` frames, window read-out of all frames at the best phase with base 0, sums per
+    segment, align_segments.  -> dict(phase, contrast, normalised, segments (the sorted labels), soft_by_segment, base, picks,
+    score, runner_up_score, ambiguous).  No verdict on ``contrast``: about 1.0 means the frames carried no phase information."""
+    n, H, W = int(frames.shape[0]), int(frames.shape[1]), int(frames.shape[2])
+    seg = np.asarray(segment_of_frame).reshape(-1)
+    if seg.size != n:
+        raise ValueError("segment_of_frame needs one entry per frame")
+    found = best_phase(_host(decoder.sync_scores_u8(frames[:max(1, int(search_frames))])), H, W)
+    soft = _host(decoder.decode_soft_window_u8(frames, L, found["phase"], int(canvas_width) // 8, base=0)).astype(np.int64)
+    labels = sorted(set(seg.tolist()))
+    by_segment = np.stack([soft[seg == s].sum(axis=0) for s in labels])
+    cands = [candidates[s] for s in labels] if isinstance(candidates, dict) else list(candidates)
+    out = align_segments(by_segment, cands, key)
+    out.update(phase=found["phase"], contrast=found["contrast"], normalised=found["normalised"], segments=labels, soft_by_segment=by_segment)
+    return out
