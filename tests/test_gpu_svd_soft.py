@@ -197,6 +197,26 @@ def test_dct_soft_on_planes_equals_the_rgb_chain(eng, H, W, layout):
         assert got.shape == (N, L) and torch.equal(got, ref) and got.any()
 
 
+@pytest.mark.parametrize("H,W,layout", [(64, 96, None), (36, 52, None), (64, 96, "i420"), (64, 96, "nv12"), (240, 320, "i420"),
+                                        (240, 320, "nv12")])
+def test_dct_soft_does_not_depend_on_the_workspace_chunk(eng, H, W, layout):
+    """3 frames in workspace chunks of 1 and of 2 (2 + 1) give the sums of the default engine's single chunk; layout None: RGB
+    frames (36x52: fringe and unaligned rows), else planes."""
+    import torch
+    from offmark.engine import DctEngine
+    rgb = cuda(np.stack([orc.synthetic_frame(H, W, 5100 + i) for i in range(N)]))
+    if layout is None:
+        call = lambda e, L: e.detect_soft(rgb, L, alpha=20, soft=garbage(N, L))  # noqa: E731
+    else:
+        planes = eng.rgb_to_yuv420(rgb, layout=layout)
+        call = lambda e, L: e.detect_soft_yuv420(planes, H, W, L, alpha=20, layout=layout, soft=garbage(N, L))  # noqa: E731
+    for L in (8, 5):
+        ref = call(eng, L)
+        assert ref.shape == (N, L) and ref.dtype == torch.int64 and ref.any()
+        for chunk in (1, 2):
+            assert torch.equal(call(DctEngine(chunk_frames=chunk), L), ref), (L, chunk)
+
+
 # ---- 5. usefulness: the noise recipe of tests/test_svd_soft_statement.py through the device ----------------------------------
 def test_soft_sums_recover_segments_the_hard_vote_loses(eng):
     from offmark.degenerator.de_shuffler import DeShuffler

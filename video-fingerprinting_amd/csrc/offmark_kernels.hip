@@ -389,13 +389,23 @@ int launch_mark_rgb8(const uint8_t *in, uint8_t *out, int n, int H, int W, const
     return OFMK_OK;
 }
 
-FinArgs fin_base(const Workspace &ws, int H, int W, double alpha) {
+// The records a finalize launch works on: kRec planes of [frames][nblk] and the per-tile sums of those frames' block DCs.
+struct RecView {
+    const float *rec;
+    const unsigned long long *ysum;    // [frames][tiles]
+    size_t plane;                      // floats between the record planes
+    int tiles;
+};
+RecView input_records(const Workspace &ws) { return {ws.rec, ws.ysum, ws.plane, ws.tiles}; }       // of the frames analyze saw
+RecView marked_records(const Workspace &ws) { return {ws.rec, ws.ysum2, ws.plane, ws.tiles}; }     // of the frames a fused mark wrote
+
+FinArgs fin_base(const RecView &v, int H, int W, double alpha) {
     FinArgs a;
     memset(&a, 0, sizeof(a));
-    a.rec = ws.rec;
-    a.plane = ws.plane;
-    a.ysum = ws.ysum;
-    a.tiles = ws.tiles;
+    a.rec = v.rec;
+    a.plane = v.plane;
+    a.ysum = v.ysum;
+    a.tiles = v.tiles;
     a.nblk = (H / 8) * (W / 8);
     a.N = (int)((long long)H * W / 64);
     a.L = 1;
@@ -404,40 +414,17 @@ FinArgs fin_base(const Workspace &ws, int H, int W, double alpha) {
     return a;
 }
 
-int finalize_detect(int f0, int cf, int H, int W, int L, double alpha, int32_t *counts, uint8_t *bits,
-                    const Workspace &ws, bool after_fused_mark, const Ctx &s) {
-    FinArgs a = fin_base(ws, H, W, alpha);
-    if (after_fused_mark) a.ysum = ws.ysum2;
-    a.L = L;
-    a.counts = counts ? counts + (size_t)f0 * L : nullptr;
-    a.bits = bits ? bits + (size_t)f0 * a.N : nullptr;
-    return launch_finalize(a, cf, s);
-}
-
-// analyze + mark for frames [f0, f0+cf); verify = also leave the marked frames' records in the
-// workspace (fused kernel), ready for finalize_detect(after_fused_mark = true)
-int embed_chunk(const void *in, void *out, int src, int f0, int cf, int H, int W, const uint8_t *wm, int n_wm,
-                const int32_t *wm_row, double alpha, const Workspace &ws, bool verify, const Ctx &s,
-                int32_t *zero_counts = nullptr, int L = 0) {
-    const size_t fs = (size_t)H * W * 3;
-    const size_t esz = src == SRC_RGB8 ? 1 : 4;
-    const char *pin = static_cast<const char *>(in) + (size_t)f0 * fs * esz;
-    char *pout = static_cast<char *>(out) + (size_t)f0 * fs * esz;
-    int rc = launch_analyze(pin, src, cf, H, W, ws, s, zero_counts ? zero_counts + (size_t)f0 * L : nullptr, L);
-    if (rc) return rc;
-    const int32_t *rows = wm_row ? wm_row + f0 : nullptr;
-    if (src == SRC_RGB8)
-        return launch_mark_rgb8(reinterpret_cast<const uint8_t *>(pin), reinterpret_cast<uint8_t *>(pout), cf, H, W, wm, n_wm,
-                                rows, alpha, ws, verify, s);
-    // float32 YUV plugin path: separate scalar stage, then the rank-1 update of channel 1
-    FinArgs a = fin_base(ws, H, W, alpha);
+// float32 YUV plugin path, in place, after launch_analyze: separate scalar stage, then the rank-1 update of channel 1
+int launch_mark_yuv32f(float *yuv, int n, int H, int W, const uint8_t *wm, int n_wm, const int32_t *wm_row, double alpha,
+                       const Workspace &ws, const Ctx &cx) {
+    FinArgs a = fin_base(input_records(ws), H, W, alpha);
     a.wm = wm;
-    a.wm_row = rows;
+    a.wm_row = wm_row;
     a.n_wm = n_wm;
     a.delta = ws.delta;
-    if ((rc = launch_finalize(a, cf, s))) return rc;
+    if (int rc = launch_finalize(a, n, cx)) return rc;
     const Geom g = make_geom(H, W, ws);
-    hipLaunchKernelGGL(mark_yuv32f_kernel, grid_2d(g.nblk, cf), dim3(kThreads), 0, s.s, reinterpret_cast<float *>(pout), g, ws.delta);
+    hipLaunchKernelGGL(mark_yuv32f_kernel, grid_2d(g.nblk, n), dim3(kThreads), 0, cx.s, yuv, g, ws.delta);
     HIP_TRY(hipGetLastError());
     return OFMK_OK;
 }
@@ -446,16 +433,6 @@ int launch_payloads(const int32_t *counts, int n, int L, int n_bits, const int32
     hipLaunchKernelGGL(degenerate_kernel, dim3((unsigned)n), dim3(kThreads), 0, s, counts, L, n_bits, perm, payload);
     HIP_TRY(hipGetLastError());
     return OFMK_OK;
-}
-
-int detect_chunk(const void *in, int src, int f0, int cf, int H, int W, int L, double alpha, int32_t *counts,
-                 uint8_t *bits, const Workspace &ws, const Ctx &s) {
-    const size_t fs = (size_t)H * W * 3;
-    const size_t esz = src == SRC_RGB8 ? 1 : 4;
-    const char *pin = static_cast<const char *>(in) + (size_t)f0 * fs * esz;
-    int rc = launch_analyze(pin, src, cf, H, W, ws, s, counts ? counts + (size_t)f0 * L : nullptr, L);
-    if (rc) return rc;
-    return finalize_detect(f0, cf, H, W, L, alpha, counts, bits, ws, false, s);
 }
 
 // The copies half of a copies kernel's arguments, for a launch that starts at frame f0 of the call's n: wm_rows is the call's
@@ -527,70 +504,30 @@ int carve_copies(void *ws, size_t bytes, int copies, int H, int W, int want_fram
     return OFMK_OK;
 }
 
-// One chunk of frames [f0, f0+cf) after launch_analyze left their records in ws.base: every copy of them, and every copy's
-// records, in one launch; zero_counts (the call's counts, or null) is cleared for these frames in every copy.
+// copy q's records of the chunk's frames, left by a mark + verify copies launch
+RecView copy_records(const CopiesWorkspace &ws, int q, int nblk) {
+    return {ws.rec + (size_t)q * ws.base.frames * nblk, ws.ysum + (size_t)q * ws.base.frames * ws.base.tiles, ws.plane, ws.base.tiles};
+}
+
+// One chunk of frames [f0, f0+cf) after launch_analyze left their records in ws (the CopiesWorkspace's base): every copy of
+// them, and every copy's records (v), in one launch.
 int launch_mark_verify_copies_rgb8(const uint8_t *in, uint8_t *out, int copies, int n, int f0, int cf, int H, int W, const uint8_t *wm,
-                                   int n_wm, const int32_t *wm_rows, double alpha, int L, int32_t *zero_counts,
-                                   const CopiesWorkspace &ws, const Ctx &cx) {
+                                   int n_wm, const int32_t *wm_rows, double alpha, int L, const CopyRecs &v, const Workspace &ws,
+                                   const Ctx &cx) {
     const size_t fs = (size_t)H * W * 3;
     const uint8_t *pin = in + (size_t)f0 * fs;
     uint8_t *pout = out + (size_t)f0 * fs;
     const int xc = tile_xcds(cx, (size_t)cf * fs);
-    const Geom g = make_geom(H, W, ws.base, cf, xc);
+    const Geom g = make_geom(H, W, ws, cf, xc);
     const dim3 grid = xcd_grid(g.nblk, cf, xc);
-    const MarkArgs m = mark_args(ws.base, H, W, wm, n_wm, nullptr, alpha);
+    const MarkArgs m = mark_args(ws, H, W, wm, n_wm, nullptr, alpha);
     const CopyArgs k = make_copy_args(copies, n, f0, wm_rows, fs, (size_t)L, (size_t)m.N);
-    CopyRecs v;
-    v.rec = ws.rec;
-    v.ysum = ws.ysum;
-    v.plane = ws.plane;
-    v.rec_stride = (size_t)ws.base.frames * g.nblk;
-    v.ysum_stride = (size_t)ws.base.frames * ws.base.tiles;
-    v.zero_counts = zero_counts ? zero_counts + (size_t)f0 * L : nullptr;
-    v.L = L;
     ScopedTiming timing(KIND_MARK_FUSED, cx);
     with_bool(aligned_rows(in, W, 1) && aligned_rows(out, W, 1), [&](auto al) {     // frame and copy strides are multiples of 8 when W is
         OFMK_TIMED_LAUNCH(timing, mark_verify_copies_rgb8_kernel<decltype(al)::value>, grid, dim3(kThreads), 0, cx.s, pin, pout, g, m, k, v);
     });
     HIP_TRY(hipGetLastError());
     return OFMK_OK;
-}
-
-// The read-out of copy q's records of frames [f0, f0+cf), left by launch_mark_verify_copies_rgb8: counts / bits are the call's
-// [copies][n][...] arrays.
-int finalize_detect_copy(int q, int n, int f0, int cf, int H, int W, int L, double alpha, int32_t *counts, uint8_t *bits,
-                         const CopiesWorkspace &ws, const Ctx &cx) {
-    FinArgs a = fin_base(ws.base, H, W, alpha);
-    a.rec = ws.rec + (size_t)q * ws.base.frames * a.nblk;
-    a.plane = ws.plane;
-    a.ysum = ws.ysum + (size_t)q * ws.base.frames * ws.base.tiles;
-    a.L = L;
-    a.counts = counts ? counts + ((size_t)q * n + f0) * L : nullptr;
-    a.bits = bits ? bits + ((size_t)q * n + f0) * a.N : nullptr;
-    return launch_finalize(a, cf, cx);
-}
-
-// The SOFT read-out of the same records (finalize_kernel<true>, the path ofmk_detect_soft_rgb8 takes after analyze) into the call's
-// int64 [copies][n][L] sums, cleared by the call.  A launch of its own: finalize's one LDS histogram serves the counts or the soft sums.
-int finalize_soft_copy(int q, int n, int f0, int cf, int H, int W, int L, double alpha, long long *soft, const CopiesWorkspace &ws,
-                       const Ctx &cx) {
-    FinArgs a = fin_base(ws.base, H, W, alpha);
-    a.rec = ws.rec + (size_t)q * ws.base.frames * a.nblk;
-    a.plane = ws.plane;
-    a.ysum = ws.ysum + (size_t)q * ws.base.frames * ws.base.tiles;
-    a.L = L;
-    a.soft = soft + ((size_t)q * n + f0) * L;
-    return launch_finalize(a, cf, cx);
-}
-
-// analyze + the soft finalize of frames [f0, f0+cf) of `in` ([n] frames; soft: their [n][L] sums, cleared by the caller)
-int detect_soft_chunk(const uint8_t *in, int f0, int cf, int H, int W, int L, double alpha, long long *soft, const Workspace &ws,
-                      const Ctx &cx) {
-    if (int rc = launch_analyze(in + (size_t)f0 * H * W * 3, SRC_RGB8, cf, H, W, ws, cx)) return rc;
-    FinArgs a = fin_base(ws, H, W, alpha);
-    a.L = L;
-    a.soft = soft + (size_t)f0 * L;
-    return launch_finalize(a, cf, cx);
 }
 
 // ---- planar YUV 4:2:0 (I420 / NV12) -------------------------------------------------------------
@@ -636,24 +573,6 @@ int launch_mark_yuv420(const uint8_t *in, uint8_t *out, int layout, int n, int H
     }); });
     HIP_TRY(hipGetLastError());
     return OFMK_OK;
-}
-
-// embed_chunk / detect_chunk for planar frames: analyze + mark, and analyze + finalize, of frames [f0, f0+cf)
-int embed_chunk_yuv420(const uint8_t *in, uint8_t *out, int layout, int f0, int cf, int H, int W, const uint8_t *wm, int n_wm,
-                       const int32_t *wm_row, double alpha, const Workspace &ws, bool verify, const Ctx &cx,
-                       int32_t *zero_counts = nullptr, int L = 0) {
-    const size_t fo = (size_t)f0 * H * W * 3 / 2;
-    int rc = launch_analyze_yuv420(in + fo, layout, cf, H, W, ws, cx, zero_counts ? zero_counts + (size_t)f0 * L : nullptr, L);
-    if (rc) return rc;
-    return launch_mark_yuv420(in + fo, out + fo, layout, cf, H, W, wm, n_wm, wm_row ? wm_row + f0 : nullptr, alpha, ws, verify, cx);
-}
-
-int detect_chunk_yuv420(const uint8_t *in, int layout, int f0, int cf, int H, int W, int L, double alpha, int32_t *counts,
-                        uint8_t *bits, const Workspace &ws, const Ctx &cx) {
-    const size_t fo = (size_t)f0 * H * W * 3 / 2;
-    int rc = launch_analyze_yuv420(in + fo, layout, cf, H, W, ws, cx, counts ? counts + (size_t)f0 * L : nullptr, L);
-    if (rc) return rc;
-    return finalize_detect(f0, cf, H, W, L, alpha, counts, bits, ws, false, cx);
 }
 
 // yuv [n] planar 4:2:0 frames <-> rgb [n][H][W][3], in the direction to_rgb says
@@ -994,25 +913,17 @@ int launch_mark_copies_yuv420(const uint8_t *in, uint8_t *out, int layout, int c
 }
 
 // launch_mark_verify_copies_rgb8 on planes (planar_copies_kernels.hiph: mark_verify_copies_yuv420_kernel): every copy of frames
-// [f0, f0+cf) and every copy's records in one launch, after launch_analyze_yuv420 left the input's records in ws.base.  The grid
-// is grid_2d's: its x extent is the tile count emit_block files the per-tile sums under, and it is ws.base.tiles (both are
+// [f0, f0+cf) and every copy's records (v) in one launch, after launch_analyze_yuv420 left the input's records in ws.  The grid
+// is grid_2d's: its x extent is the tile count emit_block files the per-tile sums under, and it is ws.tiles (both are
 // ceil(nblk / kThreads)), which is what fin_base hands finalize.
 int launch_mark_verify_copies_yuv420(const uint8_t *in, uint8_t *out, int layout, int copies, int n, int f0, int cf, int H, int W,
-                                     const uint8_t *wm, int n_wm, const int32_t *wm_rows, double alpha, int L, int32_t *zero_counts,
-                                     const CopiesWorkspace &ws, const Ctx &cx) {
-    const PGeom g = make_pgeom(layout, H, W, ws.base.plane);
-    const MarkArgs m = mark_args(ws.base, H, W, wm, n_wm, nullptr, alpha);
+                                     const uint8_t *wm, int n_wm, const int32_t *wm_rows, double alpha, int L, const CopyRecs &v,
+                                     const Workspace &ws, const Ctx &cx) {
+    const PGeom g = make_pgeom(layout, H, W, ws.plane);
+    const MarkArgs m = mark_args(ws, H, W, wm, n_wm, nullptr, alpha);
     const CopyArgs k = make_copy_args(copies, n, f0, wm_rows, g.frame_stride, (size_t)L, (size_t)m.N);
     const dim3 grid = grid_2d(g.nblk, cf);
-    if ((int)grid.x != ws.base.tiles) return fail(OFMK_E_ARG, "internal: tile count of the launch and of the workspace differ%s");
-    CopyRecs v;
-    v.rec = ws.rec;
-    v.ysum = ws.ysum;
-    v.plane = ws.plane;
-    v.rec_stride = (size_t)ws.base.frames * g.nblk;
-    v.ysum_stride = (size_t)ws.base.frames * ws.base.tiles;
-    v.zero_counts = zero_counts ? zero_counts + (size_t)f0 * L : nullptr;
-    v.L = L;
+    if ((int)grid.x != ws.tiles) return fail(OFMK_E_ARG, "internal: tile count of the launch and of the workspace differ%s");
     const size_t fo = (size_t)f0 * g.frame_stride;
     ScopedTiming timing(KIND_PLANAR_MARK, cx);
     with_fmt(layout, [&](auto fmt) {
@@ -1069,61 +980,189 @@ int svd_copies_soft(uint8_t *out, size_t frame_bytes, int copies, int n, int H, 
     });
 }
 
-// analyze + the soft finalize of frames [f0, f0+cf) of planar `in` ([n] frames; soft: their [n][L] sums, cleared by the caller)
-int detect_soft_chunk_yuv420(const uint8_t *in, int layout, int f0, int cf, int H, int W, int L, double alpha, long long *soft,
-                             const Workspace &ws, const Ctx &cx) {
-    if (int rc = launch_analyze_yuv420(in + (size_t)f0 * H * W * 3 / 2, layout, cf, H, W, ws, cx)) return rc;
-    FinArgs a = fin_base(ws, H, W, alpha);
+// ---- the DCT codec's call path: one for every frame format -------------------------------------------------------------------
+// What the frames of a call are.  An entry point makes it once, after the checks its format needs; the four leaf launchers
+// below (analyze_frames, mark_frames, mark_copies, mark_verify_copies) pick the format's own launcher, and nothing else asks:
+// everything past them works on frames of frame_bytes bytes and on the records in the workspace, which are the same for all.
+enum FrameKind { FRAMES_RGB8, FRAMES_YUV32F, FRAMES_YUV420 };
+struct FrameFmt {
+    FrameKind kind;
+    int layout;            // FRAMES_YUV420: OFMK_YUV_I420 / OFMK_YUV_NV12
+    int H, W;
+    size_t frame_bytes;
+};
+FrameFmt rgb8_frames(int H, int W) { return {FRAMES_RGB8, 0, H, W, (size_t)H * W * 3}; }
+FrameFmt yuv32f_frames(int H, int W) { return {FRAMES_YUV32F, 0, H, W, (size_t)H * W * 3 * sizeof(float)}; }
+FrameFmt yuv420_frames(int layout, int H, int W) { return {FRAMES_YUV420, layout, H, W, (size_t)H * W * 3 / 2}; }
+
+// n frames' records into ws; zero_counts: as launch_analyze
+int analyze_frames(const FrameFmt &f, const uint8_t *frames, int n, const Workspace &ws, const Ctx &cx, int32_t *zero_counts = nullptr,
+                   int L = 0) {
+    if (f.kind == FRAMES_YUV420) return launch_analyze_yuv420(frames, f.layout, n, f.H, f.W, ws, cx, zero_counts, L);
+    return launch_analyze(frames, f.kind == FRAMES_RGB8 ? SRC_RGB8 : SRC_YUV32F, n, f.H, f.W, ws, cx, zero_counts, L);
+}
+
+// Needs the input frames' records in ws (analyze_frames).  fused = true also leaves the MARKED frames' records there
+// (marked_records); the float32 frames of the plugin path have no fused kernel and are marked in place.
+int mark_frames(const FrameFmt &f, const uint8_t *in, uint8_t *out, int n, const uint8_t *wm, int n_wm, const int32_t *wm_row,
+                double alpha, const Workspace &ws, bool fused, const Ctx &cx) {
+    if (f.kind == FRAMES_RGB8) return launch_mark_rgb8(in, out, n, f.H, f.W, wm, n_wm, wm_row, alpha, ws, fused, cx);
+    if (f.kind == FRAMES_YUV420) return launch_mark_yuv420(in, out, f.layout, n, f.H, f.W, wm, n_wm, wm_row, alpha, ws, fused, cx);
+    if (fused || in != out) return fail(OFMK_E_ARG, "internal: float32 frames are marked in place, without verify%s");
+    return launch_mark_yuv32f(reinterpret_cast<float *>(out), n, f.H, f.W, wm, n_wm, wm_row, alpha, ws, cx);
+}
+
+// Every copy of frames [f0, f0+cf) of the call's n in one launch, after analyze_frames left their records in ws.
+int mark_copies(const FrameFmt &f, const uint8_t *in, uint8_t *out, int copies, int n, int f0, int cf, const uint8_t *wm, int n_wm,
+                const int32_t *wm_rows, double alpha, const Workspace &ws, const Ctx &cx) {
+    if (f.kind == FRAMES_RGB8) return launch_mark_copies_rgb8(in, out, copies, n, f0, cf, f.H, f.W, wm, n_wm, wm_rows, alpha, ws, cx);
+    if (f.kind == FRAMES_YUV420)
+        return launch_mark_copies_yuv420(in, out, f.layout, copies, n, f0, cf, f.H, f.W, wm, n_wm, wm_rows, alpha, ws, cx);
+    return fail(OFMK_E_ARG, "internal: no copies kernel for float32 frames%s");
+}
+
+// The same, and every copy's own records (copy_records) in that launch; zero_counts (the call's [copies][n][L] counts, or null)
+// is cleared for these frames in every copy.
+int mark_verify_copies(const FrameFmt &f, const uint8_t *in, uint8_t *out, int copies, int n, int f0, int cf, const uint8_t *wm,
+                       int n_wm, const int32_t *wm_rows, double alpha, int L, int32_t *zero_counts, const CopiesWorkspace &ws,
+                       const Ctx &cx) {
+    CopyRecs v;
+    v.rec = ws.rec;
+    v.ysum = ws.ysum;
+    v.plane = ws.plane;
+    v.rec_stride = (size_t)ws.base.frames * (f.H / 8) * (f.W / 8);
+    v.ysum_stride = (size_t)ws.base.frames * ws.base.tiles;
+    v.zero_counts = zero_counts ? zero_counts + (size_t)f0 * L : nullptr;
+    v.L = L;
+    if (f.kind == FRAMES_RGB8)
+        return launch_mark_verify_copies_rgb8(in, out, copies, n, f0, cf, f.H, f.W, wm, n_wm, wm_rows, alpha, L, v, ws.base, cx);
+    if (f.kind == FRAMES_YUV420)
+        return launch_mark_verify_copies_yuv420(in, out, f.layout, copies, n, f0, cf, f.H, f.W, wm, n_wm, wm_rows, alpha, L, v, ws.base, cx);
+    return fail(OFMK_E_ARG, "internal: no copies kernel for float32 frames%s");
+}
+
+// The read-out of cf frames' records.  counts / bits / soft are the call's arrays (any may be null) and these frames start at
+// row `row` of them: f0, or q * n + f0 in copy q of a copies call.  counts were cleared by the kernel that wrote the records,
+// soft by the call.  The hard outputs and the soft sums take a launch each: finalize's one LDS histogram serves the counts or
+// the soft sums.
+int read_out(const RecView &v, const FrameFmt &f, size_t row, int cf, int L, double alpha, int32_t *counts, uint8_t *bits,
+             long long *soft, const Ctx &cx) {
+    FinArgs a = fin_base(v, f.H, f.W, alpha);
     a.L = L;
-    a.soft = soft + (size_t)f0 * L;
+    if (counts || bits) {
+        a.counts = counts ? counts + row * L : nullptr;
+        a.bits = bits ? bits + row * a.N : nullptr;
+        if (int rc = launch_finalize(a, cf, cx)) return rc;
+    }
+    if (!soft) return OFMK_OK;
+    a.counts = nullptr;
+    a.bits = nullptr;
+    a.soft = soft + row * L;
     return launch_finalize(a, cf, cx);
 }
 
-// The host half of ofmk_embed_detect_copies_yuv420 and ofmk_embed_detect_copies_soft_yuv420 (want_soft: the second; its counts and
-// bits are optional and soft is required, the first needs counts or bits and has no soft).
-int embed_detect_copies_yuv420(const uint8_t *in, uint8_t *out, int layout, int copies, int n, int H, int W, const uint8_t *wm, int n_wm,
-                               const int32_t *wm_rows, double alpha, int L, int32_t *counts, uint8_t *bits, long long *soft,
-                               bool want_soft, int chunk_frames, void *workspace, size_t workspace_bytes, void *stream,
-                               const ofmk_opts *opts) {
-    if (int orc = check_opts(opts)) return orc;
-    int rc = check_embed_args(in, out, n, H, W, wm, n_wm);
+// analyze + mark of frames [f0, f0+cf) of the call; verify = also leave the marked frames' records in the workspace (fused
+// kernel), ready for read_out(marked_records(ws)).  zero_counts: the call's [n][L] counts to clear for these frames, or null.
+int embed_chunk(const FrameFmt &f, const uint8_t *in, uint8_t *out, int f0, int cf, const uint8_t *wm, int n_wm, const int32_t *wm_row,
+                double alpha, const Workspace &ws, bool verify, const Ctx &cx, int32_t *zero_counts = nullptr, int L = 0) {
+    const size_t fo = (size_t)f0 * f.frame_bytes;
+    if (int rc = analyze_frames(f, in + fo, cf, ws, cx, zero_counts ? zero_counts + (size_t)f0 * L : nullptr, L)) return rc;
+    return mark_frames(f, in + fo, out + fo, cf, wm, n_wm, wm_row ? wm_row + f0 : nullptr, alpha, ws, verify, cx);
+}
+
+// analyze + read-out of frames [f0, f0+cf) of `in` ([n] frames) into rows [f0, f0+cf) of counts / bits (hard; the analyze
+// kernel clears the counts) or of soft (cleared by the call)
+int detect_chunk(const FrameFmt &f, const uint8_t *in, int f0, int cf, int L, double alpha, int32_t *counts, uint8_t *bits,
+                 long long *soft, const Workspace &ws, const Ctx &cx) {
+    if (int rc = analyze_frames(f, in + (size_t)f0 * f.frame_bytes, cf, ws, cx, counts ? counts + (size_t)f0 * L : nullptr, L)) return rc;
+    return read_out(input_records(ws), f, (size_t)f0, cf, L, alpha, counts, bits, soft, cx);
+}
+
+// The bodies of the entry points, one per call shape; the arguments are checked by the entry point, the workspace here.
+int embed_frames(const FrameFmt &f, const uint8_t *in, uint8_t *out, int n, const uint8_t *wm, int n_wm, const int32_t *wm_row,
+                 double alpha, int chunk_frames, void *workspace, size_t workspace_bytes, void *stream, const ofmk_opts *opts) {
+    Workspace ws;
+    if (int rc = carve(workspace, workspace_bytes, f.H, f.W, chunk_frames, ws)) return rc;
+    const Ctx cx = make_ctx(stream, opts);
+    return for_chunks(n, ws.frames, [&](int f0, int cf) { return embed_chunk(f, in, out, f0, cf, wm, n_wm, wm_row, alpha, ws, false, cx); });
+}
+
+// hard (counts and / or bits) or soft: one of the two per call
+int detect_frames(const FrameFmt &f, const uint8_t *in, int n, int L, double alpha, int32_t *counts, uint8_t *bits, long long *soft,
+                  int chunk_frames, void *workspace, size_t workspace_bytes, void *stream, const ofmk_opts *opts) {
+    Workspace ws;
+    if (int rc = carve(workspace, workspace_bytes, f.H, f.W, chunk_frames, ws)) return rc;
+    const Ctx cx = make_ctx(stream, opts);
+    // counts are cleared by each chunk's analyze kernel
+    if (soft) HIP_TRY(launch_zero(soft, (size_t)n * L * sizeof(long long), cx.s));
+    return for_chunks(n, ws.frames, [&](int f0, int cf) { return detect_chunk(f, in, f0, cf, L, alpha, counts, bits, soft, ws, cx); });
+}
+
+int embed_detect_frames(const FrameFmt &f, const uint8_t *in, uint8_t *out, int n, const uint8_t *wm, int n_wm, const int32_t *wm_row,
+                        double alpha, int L, int32_t *counts, uint8_t *bits, int chunk_frames, void *workspace, size_t workspace_bytes,
+                        void *stream, const ofmk_opts *opts) {
+    Workspace ws;
+    if (int rc = carve(workspace, workspace_bytes, f.H, f.W, chunk_frames, ws)) return rc;
+    const Ctx cx = make_ctx(stream, opts);
+    return for_chunks(n, ws.frames, [&](int f0, int cf) {
+        if (!(cx.flags & OFMK_F_SEPARATE_DETECT)) {
+            if (int rc = embed_chunk(f, in, out, f0, cf, wm, n_wm, wm_row, alpha, ws, true, cx, counts, L)) return rc;
+            return read_out(marked_records(ws), f, (size_t)f0, cf, L, alpha, counts, bits, nullptr, cx);
+        }
+        if (int rc = embed_chunk(f, in, out, f0, cf, wm, n_wm, wm_row, alpha, ws, false, cx)) return rc;
+        return detect_chunk(f, out, f0, cf, L, alpha, counts, bits, nullptr, ws, cx);
+    });
+}
+
+int embed_copies_frames(const FrameFmt &f, const uint8_t *in, uint8_t *out, int copies, int n, const uint8_t *wm, int n_wm,
+                        const int32_t *wm_rows, double alpha, int chunk_frames, void *workspace, size_t workspace_bytes, void *stream,
+                        const ofmk_opts *opts) {
+    Workspace ws;
+    if (int rc = carve(workspace, workspace_bytes, f.H, f.W, chunk_frames, ws)) return rc;
+    const Ctx cx = make_ctx(stream, opts);
+    int rc = for_chunks(n, ws.frames, [&](int f0, int cf) {      // one analysis per chunk serves every copy
+        if (int rc = analyze_frames(f, in + (size_t)f0 * f.frame_bytes, cf, ws, cx)) return rc;
+        return mark_copies(f, in, out, copies, n, f0, cf, wm, n_wm, wm_rows, alpha, ws, cx);
+    });
     if (rc) return rc;
-    if ((rc = check_planar(layout, H, W, in, out))) return rc;
-    const size_t fs = (size_t)H * W * 3 / 2;
-    if ((rc = check_copies(in, out, copies, n, fs))) return rc;
-    if ((rc = want_soft ? check_soft_args(out, n, H, W, L, soft) : check_detect_args(out, n, H, W, L, counts, bits))) return rc;
+    // pixels outside the 8x8 block grid: only interleaved RGB frames have any (planes come in multiples of 8), and nothing is launched without
+    return launch_copy_fringe_copies(in, out, copies, n, f.H, f.W, cx.s);
+}
+
+// The copies-with-verify calls: counts / bits (the hard read-out of every copy) and / or soft (its int64 [copies][n][L] sums).
+int embed_detect_copies_frames(const FrameFmt &f, const uint8_t *in, uint8_t *out, int copies, int n, const uint8_t *wm, int n_wm,
+                               const int32_t *wm_rows, double alpha, int L, int32_t *counts, uint8_t *bits, long long *soft,
+                               int chunk_frames, void *workspace, size_t workspace_bytes, void *stream, const ofmk_opts *opts) {
     CopiesWorkspace ws;
-    if ((rc = carve_copies(workspace, workspace_bytes, copies, H, W, chunk_frames, ws))) return rc;
+    if (int rc = carve_copies(workspace, workspace_bytes, copies, f.H, f.W, chunk_frames, ws)) return rc;
     const Ctx cx = make_ctx(stream, opts);
     const bool hard = counts || bits;
-    const size_t N = (size_t)((long long)H * W / 64);
+    const int nblk = (f.H / 8) * (f.W / 8);
+    const size_t N = (size_t)((long long)f.H * f.W / 64);
     if (soft) HIP_TRY(launch_zero(soft, (size_t)copies * n * L * sizeof(long long), cx.s));
-    return for_chunks(n, ws.base.frames, [&](int f0, int cf) {      // one analysis of the input per chunk serves every copy
-        if (int rc = launch_analyze_yuv420(in + (size_t)f0 * fs, layout, cf, H, W, ws.base, cx)) return rc;
+    int rc = for_chunks(n, ws.base.frames, [&](int f0, int cf) {      // one analysis of the input per chunk serves every copy
+        if (int rc = analyze_frames(f, in + (size_t)f0 * f.frame_bytes, cf, ws.base, cx)) return rc;
         if (!(cx.flags & OFMK_F_SEPARATE_DETECT)) {
-            if (int rc = launch_mark_verify_copies_yuv420(in, out, layout, copies, n, f0, cf, H, W, wm, n_wm, wm_rows, alpha, L, counts, ws, cx))
-                return rc;
-            for (int q = 0; q < copies; ++q) {                    // the small launches per copy on the records the fused launch left
-                if (hard)
-                    if (int rc = finalize_detect_copy(q, n, f0, cf, H, W, L, alpha, counts, bits, ws, cx)) return rc;
-                if (soft)
-                    if (int rc = finalize_soft_copy(q, n, f0, cf, H, W, L, alpha, soft, ws, cx)) return rc;
-            }
+            if (int rc = mark_verify_copies(f, in, out, copies, n, f0, cf, wm, n_wm, wm_rows, alpha, L, counts, ws, cx)) return rc;
+            for (int q = 0; q < copies; ++q)                      // the small launches per copy on the records the fused launch left
+                if (int rc = read_out(copy_records(ws, q, nblk), f, (size_t)q * n + f0, cf, L, alpha, counts, bits, soft, cx)) return rc;
             return (int)OFMK_OK;
         }
         // the literal sequence: mark every copy, then detect (and soft-detect) each written copy (its analysis overwrites the
         // input's records, which the chunk's mark launch, earlier in the stream, has already used)
-        if (int rc = launch_mark_copies_yuv420(in, out, layout, copies, n, f0, cf, H, W, wm, n_wm, wm_rows, alpha, ws.base, cx)) return rc;
+        if (int rc = mark_copies(f, in, out, copies, n, f0, cf, wm, n_wm, wm_rows, alpha, ws.base, cx)) return rc;
         for (int q = 0; q < copies; ++q) {
-            const uint8_t *out_q = out + (size_t)q * n * fs;
+            const uint8_t *out_q = out + (size_t)q * n * f.frame_bytes;
             if (hard)
-                if (int rc = detect_chunk_yuv420(out_q, layout, f0, cf, H, W, L, alpha, counts ? counts + (size_t)q * n * L : nullptr,
-                                                 bits ? bits + (size_t)q * n * N : nullptr, ws.base, cx)) return rc;
+                if (int rc = detect_chunk(f, out_q, f0, cf, L, alpha, counts ? counts + (size_t)q * n * L : nullptr,
+                                          bits ? bits + (size_t)q * n * N : nullptr, nullptr, ws.base, cx)) return rc;
             if (soft)
-                if (int rc = detect_soft_chunk_yuv420(out_q, layout, f0, cf, H, W, L, alpha, soft + (size_t)q * n * L, ws.base, cx)) return rc;
+                if (int rc = detect_chunk(f, out_q, f0, cf, L, alpha, nullptr, nullptr, soft + (size_t)q * n * L, ws.base, cx)) return rc;
         }
         return (int)OFMK_OK;
     });
+    if (rc) return rc;
+    return launch_copy_fringe_copies(in, out, copies, n, f.H, f.W, cx.s);      // as in embed_copies_frames
 }
 
 }  // namespace
@@ -1141,25 +1180,16 @@ size_t ofmk_workspace_bytes(int frames_in_flight, int H, int W) {
 int ofmk_embed_rgb8(const uint8_t *in, uint8_t *out, int n, int H, int W, const uint8_t *wm, int n_wm,
                     const int32_t *wm_row, double alpha, int chunk_frames, void *workspace, size_t workspace_bytes,
                     void *stream, const ofmk_opts *opts) {
-    if (int orc = check_opts(opts)) return orc;
-    int rc = check_embed_args(in, out, n, H, W, wm, n_wm);
-    if (rc) return rc;
-    Workspace ws;
-    if ((rc = carve(workspace, workspace_bytes, H, W, chunk_frames, ws))) return rc;
-    const Ctx cx = make_ctx(stream, opts);
-    return for_chunks(n, ws.frames, [&](int f0, int cf) { return embed_chunk(in, out, SRC_RGB8, f0, cf, H, W, wm, n_wm, wm_row, alpha, ws, false, cx); });
+    if (int rc = check_opts(opts)) return rc;
+    if (int rc = check_embed_args(in, out, n, H, W, wm, n_wm)) return rc;
+    return embed_frames(rgb8_frames(H, W), in, out, n, wm, n_wm, wm_row, alpha, chunk_frames, workspace, workspace_bytes, stream, opts);
 }
 
 int ofmk_detect_rgb8(const uint8_t *in, int n, int H, int W, int L, double alpha, int32_t *counts, uint8_t *bits,
                      int chunk_frames, void *workspace, size_t workspace_bytes, void *stream, const ofmk_opts *opts) {
-    if (int orc = check_opts(opts)) return orc;
-    int rc = check_detect_args(in, n, H, W, L, counts, bits);
-    if (rc) return rc;
-    Workspace ws;
-    if ((rc = carve(workspace, workspace_bytes, H, W, chunk_frames, ws))) return rc;
-    const Ctx cx = make_ctx(stream, opts);
-    // counts are cleared by each chunk's analyze kernel
-    return for_chunks(n, ws.frames, [&](int f0, int cf) { return detect_chunk(in, SRC_RGB8, f0, cf, H, W, L, alpha, counts, bits, ws, cx); });
+    if (int rc = check_opts(opts)) return rc;
+    if (int rc = check_detect_args(in, n, H, W, L, counts, bits)) return rc;
+    return detect_frames(rgb8_frames(H, W), in, n, L, alpha, counts, bits, nullptr, chunk_frames, workspace, workspace_bytes, stream, opts);
 }
 
 // Build extension, not reference semantics: per payload position the sum over the frame's blocks
@@ -1167,58 +1197,37 @@ int ofmk_detect_rgb8(const uint8_t *in, int n, int H, int W, int L, double alpha
 // it is a separate entry point from the hard-decision counts.
 int ofmk_detect_soft_rgb8(const uint8_t *in, int n, int H, int W, int L, double alpha, long long *soft, int chunk_frames,
                           void *workspace, size_t workspace_bytes, void *stream, const ofmk_opts *opts) {
-    if (int orc = check_opts(opts)) return orc;
-    int rc = check_soft_args(in, n, H, W, L, soft);
-    if (rc) return rc;
-    Workspace ws;
-    if ((rc = carve(workspace, workspace_bytes, H, W, chunk_frames, ws))) return rc;
-    const Ctx cx = make_ctx(stream, opts);
-    HIP_TRY(launch_zero(soft, (size_t)n * L * sizeof(long long), cx.s));
-    return for_chunks(n, ws.frames, [&](int f0, int cf) { return detect_soft_chunk(in, f0, cf, H, W, L, alpha, soft, ws, cx); });
+    if (int rc = check_opts(opts)) return rc;
+    if (int rc = check_soft_args(in, n, H, W, L, soft)) return rc;
+    return detect_frames(rgb8_frames(H, W), in, n, L, alpha, nullptr, nullptr, soft, chunk_frames, workspace, workspace_bytes, stream, opts);
 }
 
 int ofmk_embed_detect_rgb8(const uint8_t *in, uint8_t *out, int n, int H, int W, const uint8_t *wm, int n_wm,
                            const int32_t *wm_row, double alpha, int L, int32_t *counts, uint8_t *bits,
                            int chunk_frames, void *workspace, size_t workspace_bytes, void *stream,
                            const ofmk_opts *opts) {
-    if (int orc = check_opts(opts)) return orc;
-    int rc = check_embed_args(in, out, n, H, W, wm, n_wm);
-    if (rc) return rc;
-    if ((rc = check_detect_args(out, n, H, W, L, counts, bits))) return rc;
-    Workspace ws;
-    if ((rc = carve(workspace, workspace_bytes, H, W, chunk_frames, ws))) return rc;
-    const Ctx cx = make_ctx(stream, opts);
-    return for_chunks(n, ws.frames, [&](int f0, int cf) {
-        if (!(cx.flags & OFMK_F_SEPARATE_DETECT)) {
-            if (int rc = embed_chunk(in, out, SRC_RGB8, f0, cf, H, W, wm, n_wm, wm_row, alpha, ws, true, cx, counts, L)) return rc;
-            return finalize_detect(f0, cf, H, W, L, alpha, counts, bits, ws, true, cx);
-        }
-        if (int rc = embed_chunk(in, out, SRC_RGB8, f0, cf, H, W, wm, n_wm, wm_row, alpha, ws, false, cx)) return rc;
-        return detect_chunk(out, SRC_RGB8, f0, cf, H, W, L, alpha, counts, bits, ws, cx);
-    });
+    if (int rc = check_opts(opts)) return rc;
+    if (int rc = check_embed_args(in, out, n, H, W, wm, n_wm)) return rc;
+    if (int rc = check_detect_args(out, n, H, W, L, counts, bits)) return rc;
+    return embed_detect_frames(rgb8_frames(H, W), in, out, n, wm, n_wm, wm_row, alpha, L, counts, bits, chunk_frames, workspace,
+                               workspace_bytes, stream, opts);
 }
 
 int ofmk_encode_yuv32f(float *yuv, int n, int H, int W, const uint8_t *wm, int n_wm, const int32_t *wm_row,
                        double alpha, int chunk_frames, void *workspace, size_t workspace_bytes, void *stream,
                        const ofmk_opts *opts) {
-    if (int orc = check_opts(opts)) return orc;
-    int rc = check_embed_args(yuv, yuv, n, H, W, wm, n_wm);
-    if (rc) return rc;
-    Workspace ws;
-    if ((rc = carve(workspace, workspace_bytes, H, W, chunk_frames, ws))) return rc;
-    const Ctx cx = make_ctx(stream, opts);
-    return for_chunks(n, ws.frames, [&](int f0, int cf) { return embed_chunk(yuv, yuv, SRC_YUV32F, f0, cf, H, W, wm, n_wm, wm_row, alpha, ws, false, cx); });
+    if (int rc = check_opts(opts)) return rc;
+    if (int rc = check_embed_args(yuv, yuv, n, H, W, wm, n_wm)) return rc;
+    uint8_t *p = reinterpret_cast<uint8_t *>(yuv);
+    return embed_frames(yuv32f_frames(H, W), p, p, n, wm, n_wm, wm_row, alpha, chunk_frames, workspace, workspace_bytes, stream, opts);
 }
 
 int ofmk_decode_yuv32f(const float *yuv, int n, int H, int W, int L, double alpha, int32_t *counts, uint8_t *bits,
                        int chunk_frames, void *workspace, size_t workspace_bytes, void *stream, const ofmk_opts *opts) {
-    if (int orc = check_opts(opts)) return orc;
-    int rc = check_detect_args(yuv, n, H, W, L, counts, bits);
-    if (rc) return rc;
-    Workspace ws;
-    if ((rc = carve(workspace, workspace_bytes, H, W, chunk_frames, ws))) return rc;
-    const Ctx cx = make_ctx(stream, opts);
-    return for_chunks(n, ws.frames, [&](int f0, int cf) { return detect_chunk(yuv, SRC_YUV32F, f0, cf, H, W, L, alpha, counts, bits, ws, cx); });
+    if (int rc = check_opts(opts)) return rc;
+    if (int rc = check_detect_args(yuv, n, H, W, L, counts, bits)) return rc;
+    return detect_frames(yuv32f_frames(H, W), reinterpret_cast<const uint8_t *>(yuv), n, L, alpha, counts, bits, nullptr, chunk_frames,
+                         workspace, workspace_bytes, stream, opts);
 }
 
 int ofmk_debug_planes(const void *frame, int src_is_yuv32f, int H, int W, double alpha, const uint8_t *wm,
@@ -1232,8 +1241,9 @@ int ofmk_debug_planes(const void *frame, int src_is_yuv32f, int H, int W, double
     Workspace ws;
     if ((rc = carve(workspace, workspace_bytes, H, W, 1, ws))) return rc;
     const Ctx cx = make_ctx(stream, opts);
-    if ((rc = launch_analyze(frame, src_is_yuv32f ? SRC_YUV32F : SRC_RGB8, 1, H, W, ws, cx))) return rc;
-    FinArgs a = fin_base(ws, H, W, alpha);
+    const FrameFmt f = src_is_yuv32f ? yuv32f_frames(H, W) : rgb8_frames(H, W);
+    if ((rc = analyze_frames(f, static_cast<const uint8_t *>(frame), 1, ws, cx))) return rc;
+    FinArgs a = fin_base(input_records(ws), H, W, alpha);
     a.wm = wm;
     a.y_dc = y_dc;
     a.lum = lum_mask;
@@ -1253,7 +1263,7 @@ int ofmk_stage_analyze_rgb8(const uint8_t *in, int n, int H, int W, void *worksp
     Workspace ws;
     if ((rc = carve(workspace, workspace_bytes, H, W, n, ws))) return rc;
     if (ws.frames < n) return fail(OFMK_E_WORKSPACE, "stage call needs workspace for all n frames%s");
-    return launch_analyze(in, SRC_RGB8, n, H, W, ws, make_ctx(stream, opts));
+    return analyze_frames(rgb8_frames(H, W), in, n, ws, make_ctx(stream, opts));
 }
 
 int ofmk_stage_mark_rgb8(const uint8_t *in, uint8_t *out, int n, int H, int W, const uint8_t *wm, double alpha,
@@ -1264,7 +1274,7 @@ int ofmk_stage_mark_rgb8(const uint8_t *in, uint8_t *out, int n, int H, int W, c
     Workspace ws;
     if ((rc = carve(workspace, workspace_bytes, H, W, n, ws))) return rc;
     if (ws.frames < n) return fail(OFMK_E_WORKSPACE, "stage call needs workspace for all n frames%s");
-    return launch_mark_rgb8(in, out, n, H, W, wm, 1, nullptr, alpha, ws, fused != 0, make_ctx(stream, opts));
+    return mark_frames(rgb8_frames(H, W), in, out, n, wm, 1, nullptr, alpha, ws, fused != 0, make_ctx(stream, opts));
 }
 
 int ofmk_svd_embed_rgb8(const uint8_t *in, uint8_t *out, int n, int H, int W, const uint8_t *wm, int n_wm,
@@ -1384,19 +1394,11 @@ int ofmk_svd_embed_detect_rgb8(const uint8_t *in, uint8_t *out, int n, int H, in
 int ofmk_embed_copies_rgb8(const uint8_t *in, uint8_t *out, int copies, int n, int H, int W, const uint8_t *wm, int n_wm,
                            const int32_t *wm_rows, double alpha, int chunk_frames, void *workspace, size_t workspace_bytes,
                            void *stream, const ofmk_opts *opts) {
-    if (int orc = check_opts(opts)) return orc;
-    int rc = check_embed_args(in, out, n, H, W, wm, n_wm);
-    if (rc) return rc;
-    if ((rc = check_copies(in, out, copies, n, (size_t)H * W * 3))) return rc;
-    Workspace ws;
-    if ((rc = carve(workspace, workspace_bytes, H, W, chunk_frames, ws))) return rc;
-    const Ctx cx = make_ctx(stream, opts);
-    rc = for_chunks(n, ws.frames, [&](int f0, int cf) {      // one analysis per chunk serves every copy
-        if (int rc = launch_analyze(in + (size_t)f0 * H * W * 3, SRC_RGB8, cf, H, W, ws, cx)) return rc;
-        return launch_mark_copies_rgb8(in, out, copies, n, f0, cf, H, W, wm, n_wm, wm_rows, alpha, ws, cx);
-    });
-    if (rc) return rc;
-    return launch_copy_fringe_copies(in, out, copies, n, H, W, cx.s);
+    if (int rc = check_opts(opts)) return rc;
+    if (int rc = check_embed_args(in, out, n, H, W, wm, n_wm)) return rc;
+    const FrameFmt f = rgb8_frames(H, W);
+    if (int rc = check_copies(in, out, copies, n, f.frame_bytes)) return rc;
+    return embed_copies_frames(f, in, out, copies, n, wm, n_wm, wm_rows, alpha, chunk_frames, workspace, workspace_bytes, stream, opts);
 }
 
 size_t ofmk_copies_workspace_bytes(int frames_in_flight, int copies, int H, int W) {
@@ -1407,75 +1409,26 @@ size_t ofmk_copies_workspace_bytes(int frames_in_flight, int copies, int H, int 
 int ofmk_embed_detect_copies_rgb8(const uint8_t *in, uint8_t *out, int copies, int n, int H, int W, const uint8_t *wm, int n_wm,
                                   const int32_t *wm_rows, double alpha, int L, int32_t *counts, uint8_t *bits, int chunk_frames,
                                   void *workspace, size_t workspace_bytes, void *stream, const ofmk_opts *opts) {
-    if (int orc = check_opts(opts)) return orc;
-    int rc = check_embed_args(in, out, n, H, W, wm, n_wm);
-    if (rc) return rc;
-    if ((rc = check_copies(in, out, copies, n, (size_t)H * W * 3))) return rc;
-    if ((rc = check_detect_args(out, n, H, W, L, counts, bits))) return rc;
-    CopiesWorkspace ws;
-    if ((rc = carve_copies(workspace, workspace_bytes, copies, H, W, chunk_frames, ws))) return rc;
-    const Ctx cx = make_ctx(stream, opts);
-    const size_t fs = (size_t)H * W * 3;
-    const size_t N = (size_t)((long long)H * W / 64);
-    rc = for_chunks(n, ws.base.frames, [&](int f0, int cf) {      // one analysis of the input per chunk serves every copy
-        if (int rc = launch_analyze(in + (size_t)f0 * fs, SRC_RGB8, cf, H, W, ws.base, cx)) return rc;
-        if (!(cx.flags & OFMK_F_SEPARATE_DETECT)) {
-            if (int rc = launch_mark_verify_copies_rgb8(in, out, copies, n, f0, cf, H, W, wm, n_wm, wm_rows, alpha, L, counts, ws, cx)) return rc;
-            for (int q = 0; q < copies; ++q)
-                if (int rc = finalize_detect_copy(q, n, f0, cf, H, W, L, alpha, counts, bits, ws, cx)) return rc;
-            return (int)OFMK_OK;
-        }
-        // the literal sequence: mark every copy, then detect each written copy (its analysis overwrites the input's records,
-        // which the chunk's mark launch, earlier in the stream, has already used)
-        if (int rc = launch_mark_copies_rgb8(in, out, copies, n, f0, cf, H, W, wm, n_wm, wm_rows, alpha, ws.base, cx)) return rc;
-        for (int q = 0; q < copies; ++q)
-            if (int rc = detect_chunk(out + (size_t)q * n * fs, SRC_RGB8, f0, cf, H, W, L, alpha, counts ? counts + (size_t)q * n * L : nullptr,
-                                      bits ? bits + (size_t)q * n * N : nullptr, ws.base, cx)) return rc;
-        return (int)OFMK_OK;
-    });
-    if (rc) return rc;
-    return launch_copy_fringe_copies(in, out, copies, n, H, W, cx.s);
+    if (int rc = check_opts(opts)) return rc;
+    if (int rc = check_embed_args(in, out, n, H, W, wm, n_wm)) return rc;
+    const FrameFmt f = rgb8_frames(H, W);
+    if (int rc = check_copies(in, out, copies, n, f.frame_bytes)) return rc;
+    if (int rc = check_detect_args(out, n, H, W, L, counts, bits)) return rc;
+    return embed_detect_copies_frames(f, in, out, copies, n, wm, n_wm, wm_rows, alpha, L, counts, bits, nullptr, chunk_frames, workspace,
+                                      workspace_bytes, stream, opts);
 }
 
+// counts and bits are optional here, soft is required
 int ofmk_embed_detect_copies_soft_rgb8(const uint8_t *in, uint8_t *out, int copies, int n, int H, int W, const uint8_t *wm, int n_wm,
                                        const int32_t *wm_rows, double alpha, int L, int32_t *counts, uint8_t *bits, long long *soft,
                                        int chunk_frames, void *workspace, size_t workspace_bytes, void *stream, const ofmk_opts *opts) {
-    if (int orc = check_opts(opts)) return orc;
-    int rc = check_embed_args(in, out, n, H, W, wm, n_wm);
-    if (rc) return rc;
-    if ((rc = check_copies(in, out, copies, n, (size_t)H * W * 3))) return rc;
-    if ((rc = check_soft_args(out, n, H, W, L, soft))) return rc;
-    CopiesWorkspace ws;
-    if ((rc = carve_copies(workspace, workspace_bytes, copies, H, W, chunk_frames, ws))) return rc;
-    const Ctx cx = make_ctx(stream, opts);
-    const bool hard = counts || bits;
-    const size_t fs = (size_t)H * W * 3;
-    const size_t N = (size_t)((long long)H * W / 64);
-    HIP_TRY(launch_zero(soft, (size_t)copies * n * L * sizeof(long long), cx.s));
-    rc = for_chunks(n, ws.base.frames, [&](int f0, int cf) {      // one analysis of the input per chunk serves every copy
-        if (int rc = launch_analyze(in + (size_t)f0 * fs, SRC_RGB8, cf, H, W, ws.base, cx)) return rc;
-        if (!(cx.flags & OFMK_F_SEPARATE_DETECT)) {
-            if (int rc = launch_mark_verify_copies_rgb8(in, out, copies, n, f0, cf, H, W, wm, n_wm, wm_rows, alpha, L, counts, ws, cx)) return rc;
-            for (int q = 0; q < copies; ++q) {                    // two small launches per copy on the records the fused launch left
-                if (hard)
-                    if (int rc = finalize_detect_copy(q, n, f0, cf, H, W, L, alpha, counts, bits, ws, cx)) return rc;
-                if (int rc = finalize_soft_copy(q, n, f0, cf, H, W, L, alpha, soft, ws, cx)) return rc;
-            }
-            return (int)OFMK_OK;
-        }
-        // the literal sequence: mark every copy, then detect and soft-detect each written copy
-        if (int rc = launch_mark_copies_rgb8(in, out, copies, n, f0, cf, H, W, wm, n_wm, wm_rows, alpha, ws.base, cx)) return rc;
-        for (int q = 0; q < copies; ++q) {
-            const uint8_t *out_q = out + (size_t)q * n * fs;
-            if (hard)
-                if (int rc = detect_chunk(out_q, SRC_RGB8, f0, cf, H, W, L, alpha, counts ? counts + (size_t)q * n * L : nullptr,
-                                          bits ? bits + (size_t)q * n * N : nullptr, ws.base, cx)) return rc;
-            if (int rc = detect_soft_chunk(out_q, f0, cf, H, W, L, alpha, soft + (size_t)q * n * L, ws.base, cx)) return rc;
-        }
-        return (int)OFMK_OK;
-    });
-    if (rc) return rc;
-    return launch_copy_fringe_copies(in, out, copies, n, H, W, cx.s);
+    if (int rc = check_opts(opts)) return rc;
+    if (int rc = check_embed_args(in, out, n, H, W, wm, n_wm)) return rc;
+    const FrameFmt f = rgb8_frames(H, W);
+    if (int rc = check_copies(in, out, copies, n, f.frame_bytes)) return rc;
+    if (int rc = check_soft_args(out, n, H, W, L, soft)) return rc;
+    return embed_detect_copies_frames(f, in, out, copies, n, wm, n_wm, wm_rows, alpha, L, counts, bits, soft, chunk_frames, workspace,
+                                      workspace_bytes, stream, opts);
 }
 
 int ofmk_svd_embed_copies_soft_rgb8(const uint8_t *in, uint8_t *out, int copies, int n, int H, int W, const uint8_t *wm, int n_wm,
@@ -1602,68 +1555,41 @@ int ofmk_payloads_from_partial_counts(const int32_t *partials, int tiles, int n,
 int ofmk_embed_yuv420(const uint8_t *in, uint8_t *out, int layout, int n, int H, int W, const uint8_t *wm, int n_wm,
                       const int32_t *wm_row, double alpha, int chunk_frames, void *workspace, size_t workspace_bytes,
                       void *stream, const ofmk_opts *opts) {
-    if (int orc = check_opts(opts)) return orc;
-    int rc = check_embed_args(in, out, n, H, W, wm, n_wm);
-    if (rc) return rc;
-    if ((rc = check_planar(layout, H, W, in, out))) return rc;
-    Workspace ws;
-    if ((rc = carve(workspace, workspace_bytes, H, W, chunk_frames, ws))) return rc;
-    const Ctx cx = make_ctx(stream, opts);
-    return for_chunks(n, ws.frames, [&](int f0, int cf) { return embed_chunk_yuv420(in, out, layout, f0, cf, H, W, wm, n_wm, wm_row, alpha, ws, false, cx); });
+    if (int rc = check_opts(opts)) return rc;
+    if (int rc = check_embed_args(in, out, n, H, W, wm, n_wm)) return rc;
+    if (int rc = check_planar(layout, H, W, in, out)) return rc;
+    return embed_frames(yuv420_frames(layout, H, W), in, out, n, wm, n_wm, wm_row, alpha, chunk_frames, workspace, workspace_bytes, stream,
+                        opts);
 }
 
 int ofmk_detect_yuv420(const uint8_t *in, int layout, int n, int H, int W, int L, double alpha, int32_t *counts, uint8_t *bits,
                        int chunk_frames, void *workspace, size_t workspace_bytes, void *stream, const ofmk_opts *opts) {
-    if (int orc = check_opts(opts)) return orc;
-    int rc = check_detect_args(in, n, H, W, L, counts, bits);
-    if (rc) return rc;
-    if ((rc = check_planar(layout, H, W, in, nullptr))) return rc;
-    Workspace ws;
-    if ((rc = carve(workspace, workspace_bytes, H, W, chunk_frames, ws))) return rc;
-    const Ctx cx = make_ctx(stream, opts);
-    return for_chunks(n, ws.frames, [&](int f0, int cf) { return detect_chunk_yuv420(in, layout, f0, cf, H, W, L, alpha, counts, bits, ws, cx); });
+    if (int rc = check_opts(opts)) return rc;
+    if (int rc = check_detect_args(in, n, H, W, L, counts, bits)) return rc;
+    if (int rc = check_planar(layout, H, W, in, nullptr)) return rc;
+    return detect_frames(yuv420_frames(layout, H, W), in, n, L, alpha, counts, bits, nullptr, chunk_frames, workspace, workspace_bytes,
+                         stream, opts);
 }
 
 // The DCT codec's soft metric (ofmk_detect_soft_rgb8) for planar callers: the planar analysis, then the same finalize.
 int ofmk_detect_soft_yuv420(const uint8_t *in, int layout, int n, int H, int W, int L, double alpha, long long *soft, int chunk_frames,
                             void *workspace, size_t workspace_bytes, void *stream, const ofmk_opts *opts) {
-    if (int orc = check_opts(opts)) return orc;
-    int rc = check_soft_args(in, n, H, W, L, soft);
-    if (rc) return rc;
-    if ((rc = check_planar(layout, H, W, in, nullptr))) return rc;
-    Workspace ws;
-    if ((rc = carve(workspace, workspace_bytes, H, W, chunk_frames, ws))) return rc;
-    const Ctx cx = make_ctx(stream, opts);
-    HIP_TRY(launch_zero(soft, (size_t)n * L * sizeof(long long), cx.s));
-    const size_t fs = (size_t)H * W * 3 / 2;
-    return for_chunks(n, ws.frames, [&](int f0, int cf) {
-        if (int rc = launch_analyze_yuv420(in + (size_t)f0 * fs, layout, cf, H, W, ws, cx)) return rc;
-        FinArgs a = fin_base(ws, H, W, alpha);
-        a.L = L;
-        a.soft = soft + (size_t)f0 * L;
-        return launch_finalize(a, cf, cx);
-    });
+    if (int rc = check_opts(opts)) return rc;
+    if (int rc = check_soft_args(in, n, H, W, L, soft)) return rc;
+    if (int rc = check_planar(layout, H, W, in, nullptr)) return rc;
+    return detect_frames(yuv420_frames(layout, H, W), in, n, L, alpha, nullptr, nullptr, soft, chunk_frames, workspace, workspace_bytes,
+                         stream, opts);
 }
 
 int ofmk_embed_detect_yuv420(const uint8_t *in, uint8_t *out, int layout, int n, int H, int W, const uint8_t *wm, int n_wm,
                              const int32_t *wm_row, double alpha, int L, int32_t *counts, uint8_t *bits, int chunk_frames,
                              void *workspace, size_t workspace_bytes, void *stream, const ofmk_opts *opts) {
-    if (int orc = check_opts(opts)) return orc;
-    int rc = check_embed_args(in, out, n, H, W, wm, n_wm);
-    if (rc) return rc;
-    if ((rc = check_detect_args(out, n, H, W, L, counts, bits))) return rc;
-    if ((rc = check_planar(layout, H, W, in, out))) return rc;
-    Workspace ws;
-    if ((rc = carve(workspace, workspace_bytes, H, W, chunk_frames, ws))) return rc;
-    const Ctx cx = make_ctx(stream, opts);
-    return for_chunks(n, ws.frames, [&](int f0, int cf) {
-        if (!(cx.flags & OFMK_F_SEPARATE_DETECT)) {
-            if (int rc = embed_chunk_yuv420(in, out, layout, f0, cf, H, W, wm, n_wm, wm_row, alpha, ws, true, cx, counts, L)) return rc;
-            return finalize_detect(f0, cf, H, W, L, alpha, counts, bits, ws, true, cx);
-        }
-        if (int rc = embed_chunk_yuv420(in, out, layout, f0, cf, H, W, wm, n_wm, wm_row, alpha, ws, false, cx)) return rc;
-        return detect_chunk_yuv420(out, layout, f0, cf, H, W, L, alpha, counts, bits, ws, cx);
-    });
+    if (int rc = check_opts(opts)) return rc;
+    if (int rc = check_embed_args(in, out, n, H, W, wm, n_wm)) return rc;
+    if (int rc = check_planar(layout, H, W, in, out)) return rc;
+    if (int rc = check_detect_args(out, n, H, W, L, counts, bits)) return rc;
+    return embed_detect_frames(yuv420_frames(layout, H, W), in, out, n, wm, n_wm, wm_row, alpha, L, counts, bits, chunk_frames, workspace,
+                               workspace_bytes, stream, opts);
 }
 
 // ---- DwtDctSvd codec on planar YUV 4:2:0: the rgb8 SVD calls' conventions, the yuv420 calls' layout ----------------------------
@@ -1724,33 +1650,39 @@ int ofmk_svd_embed_detect_yuv420(const uint8_t *in, uint8_t *out, int layout, in
 int ofmk_embed_copies_yuv420(const uint8_t *in, uint8_t *out, int layout, int copies, int n, int H, int W, const uint8_t *wm, int n_wm,
                              const int32_t *wm_rows, double alpha, int chunk_frames, void *workspace, size_t workspace_bytes,
                              void *stream, const ofmk_opts *opts) {
-    if (int orc = check_opts(opts)) return orc;
-    int rc = check_embed_args(in, out, n, H, W, wm, n_wm);
-    if (rc) return rc;
-    if ((rc = check_planar(layout, H, W, in, out))) return rc;
-    if ((rc = check_copies(in, out, copies, n, (size_t)H * W * 3 / 2))) return rc;
-    Workspace ws;
-    if ((rc = carve(workspace, workspace_bytes, H, W, chunk_frames, ws))) return rc;
-    const Ctx cx = make_ctx(stream, opts);
-    return for_chunks(n, ws.frames, [&](int f0, int cf) {      // one analysis per chunk serves every copy
-        if (int rc = launch_analyze_yuv420(in + (size_t)f0 * H * W * 3 / 2, layout, cf, H, W, ws, cx)) return rc;
-        return launch_mark_copies_yuv420(in, out, layout, copies, n, f0, cf, H, W, wm, n_wm, wm_rows, alpha, ws, cx);
-    });
+    if (int rc = check_opts(opts)) return rc;
+    if (int rc = check_embed_args(in, out, n, H, W, wm, n_wm)) return rc;
+    if (int rc = check_planar(layout, H, W, in, out)) return rc;
+    const FrameFmt f = yuv420_frames(layout, H, W);
+    if (int rc = check_copies(in, out, copies, n, f.frame_bytes)) return rc;
+    return embed_copies_frames(f, in, out, copies, n, wm, n_wm, wm_rows, alpha, chunk_frames, workspace, workspace_bytes, stream, opts);
 }
 
 int ofmk_embed_detect_copies_yuv420(const uint8_t *in, uint8_t *out, int layout, int copies, int n, int H, int W, const uint8_t *wm,
                                     int n_wm, const int32_t *wm_rows, double alpha, int L, int32_t *counts, uint8_t *bits,
                                     int chunk_frames, void *workspace, size_t workspace_bytes, void *stream, const ofmk_opts *opts) {
-    return embed_detect_copies_yuv420(in, out, layout, copies, n, H, W, wm, n_wm, wm_rows, alpha, L, counts, bits, nullptr, false,
-                                      chunk_frames, workspace, workspace_bytes, stream, opts);
+    if (int rc = check_opts(opts)) return rc;
+    if (int rc = check_embed_args(in, out, n, H, W, wm, n_wm)) return rc;
+    if (int rc = check_planar(layout, H, W, in, out)) return rc;
+    const FrameFmt f = yuv420_frames(layout, H, W);
+    if (int rc = check_copies(in, out, copies, n, f.frame_bytes)) return rc;
+    if (int rc = check_detect_args(out, n, H, W, L, counts, bits)) return rc;
+    return embed_detect_copies_frames(f, in, out, copies, n, wm, n_wm, wm_rows, alpha, L, counts, bits, nullptr, chunk_frames, workspace,
+                                      workspace_bytes, stream, opts);
 }
 
 int ofmk_embed_detect_copies_soft_yuv420(const uint8_t *in, uint8_t *out, int layout, int copies, int n, int H, int W, const uint8_t *wm,
                                          int n_wm, const int32_t *wm_rows, double alpha, int L, int32_t *counts, uint8_t *bits,
                                          long long *soft, int chunk_frames, void *workspace, size_t workspace_bytes, void *stream,
                                          const ofmk_opts *opts) {
-    return embed_detect_copies_yuv420(in, out, layout, copies, n, H, W, wm, n_wm, wm_rows, alpha, L, counts, bits, soft, true,
-                                      chunk_frames, workspace, workspace_bytes, stream, opts);
+    if (int rc = check_opts(opts)) return rc;
+    if (int rc = check_embed_args(in, out, n, H, W, wm, n_wm)) return rc;
+    if (int rc = check_planar(layout, H, W, in, out)) return rc;
+    const FrameFmt f = yuv420_frames(layout, H, W);
+    if (int rc = check_copies(in, out, copies, n, f.frame_bytes)) return rc;
+    if (int rc = check_soft_args(out, n, H, W, L, soft)) return rc;
+    return embed_detect_copies_frames(f, in, out, copies, n, wm, n_wm, wm_rows, alpha, L, counts, bits, soft, chunk_frames, workspace,
+                                      workspace_bytes, stream, opts);
 }
 
 int ofmk_svd_embed_copies_yuv420(const uint8_t *in, uint8_t *out, int layout, int copies, int n, int H, int W, const uint8_t *wm,

@@ -173,7 +173,7 @@ class DctEngine:
             return "xcd"
         return None
 
-    def _o(self, launch_bytes=None, fused=True, extra_flags=0):
+    def _o(self, launch_bytes=None, extra_flags=0):
         """ctypes argument for this call's ofmk_opts: the engine's opts (flags, timing) plus, for a call that runs the frame-writing
         DCT kernel (``launch_bytes`` = bytes of frames per launch), the engine's forced tile order, if it has one (else none: the
         library's static rule); ``extra_flags``: flags of this one call (OFMK_F_PARTIAL_COUNTS)."""
@@ -195,10 +195,6 @@ class DctEngine:
         self._opts_cache = o                                  # alive until the next call
         return _hip.opts_ref(o)
 
-    def _launch_marking(self, launch, frames, out, launch_bytes, fused, chunks=1):
-        """Issue a marking call: ``launch(opts)`` enqueues it with this call's ofmk_opts."""
-        launch(self._o(launch_bytes, fused))
-
     def _check_frames(self, frames, dtype):
         t = self.torch
         if not (isinstance(frames, t.Tensor) and frames.is_cuda and frames.dtype == dtype
@@ -207,42 +203,33 @@ class DctEngine:
         n, H, W, _ = frames.shape
         return n, H, W
 
-    def _out(self, out, like, shape=None):
-        """The destination of a call: a fresh tensor, or the caller's, which must be a contiguous CUDA tensor of the
-        expected shape (default: ``like``'s), ``like``'s dtype and device -- the kernels write through its raw pointer."""
+    def _buffer(self, name, given, shape, dtype, device):
+        """An output of a call: a fresh tensor, or the caller's, which must be a contiguous CUDA tensor of exactly this shape,
+        dtype and device -- the kernels write through its raw pointer."""
         t = self.torch
-        shape = tuple(like.shape if shape is None else shape)
-        if out is None:
-            return t.empty(shape, dtype=like.dtype, device=like.device)
-        if not (isinstance(out, t.Tensor) and out.is_cuda and out.device == like.device and out.dtype == like.dtype
-                and tuple(out.shape) == shape and out.is_contiguous()):
-            raise ValueError(f"out must be a contiguous CUDA {like.dtype} tensor of shape {shape} on {like.device}")
-        return out
+        shape = tuple(shape)
+        if given is None:
+            return t.empty(shape, dtype=dtype, device=device)
+        if not (isinstance(given, t.Tensor) and given.is_cuda and given.device == device and given.dtype == dtype
+                and tuple(given.shape) == shape and given.is_contiguous()):
+            raise ValueError(f"{name} must be a contiguous CUDA {dtype} tensor of shape {shape} on {device}")
+        return given
+
+    def _out(self, out, like, shape=None):
+        """The destination of a call: the expected shape (default: ``like``'s), ``like``'s dtype and device."""
+        return self._buffer("out", out, like.shape if shape is None else shape, like.dtype, like.device)
 
     def _counts(self, counts, n, L, copies=None):
         """The position sums of a call: a fresh int32 [n, L] tensor, or the caller's (a pipeline that hands them to another
         stream keeps its own buffers: torch's allocator would hand a per-call tensor's block out again on the issuing stream).
         ``copies``: one such array per copy, [copies, n, L]."""
-        t = self.torch
-        shape = (n, L) if copies is None else (copies, n, L)
-        if counts is None:
-            return t.empty(shape, dtype=t.int32, device=self.device)
-        if not (isinstance(counts, t.Tensor) and counts.is_cuda and counts.device == self.device and counts.dtype == t.int32
-                and tuple(counts.shape) == shape and counts.is_contiguous()):
-            raise ValueError(f"counts must be a contiguous CUDA int32 tensor of shape {shape} on {self.device}")
-        return counts
+        return self._buffer("counts", counts, (n, L) if copies is None else (copies, n, L), self.torch.int32, self.device)
 
     def _soft(self, soft, n, L, copies=None):
         """The soft sums of a call: a fresh int64 [n, L] tensor, or the caller's (whatever it holds: the library clears it).
         ``copies``: one such array per copy, [copies, n, L]; ``soft`` may then be True (a fresh tensor)."""
-        t = self.torch
         shape = (n, L) if copies is None else (copies, n, L)
-        if soft is None or soft is True:
-            return t.empty(shape, dtype=t.int64, device=self.device)
-        if not (isinstance(soft, t.Tensor) and soft.is_cuda and soft.device == self.device and soft.dtype == t.int64
-                and tuple(soft.shape) == shape and soft.is_contiguous()):
-            raise ValueError(f"soft must be a contiguous CUDA int64 tensor of shape {shape} on {self.device}")
-        return soft
+        return self._buffer("soft", None if soft is True else soft, shape, self.torch.int64, self.device)
 
     def _layout(self, layout):
         try:
@@ -291,12 +278,9 @@ class DctEngine:
         out = self._out(out, frames)
         cf = self._chunk(n, H, W)
         ws = self.workspace(H, W, cf)
-        stream = _hip.current_stream()
-
-        def launch(o):
-            _hip.check(self.lib.ofmk_embed_rgb8(frames.data_ptr(), out.data_ptr(), n, H, W, wm.data_ptr(), wm.shape[0],
-                                                _hip.ptr(rows), float(alpha), cf, ws.data_ptr(), ws.numel(), stream, o))
-        self._launch_marking(launch, frames, out, min(cf, n) * H * W * 3, False, chunks=-(-n // cf))
+        _hip.check(self.lib.ofmk_embed_rgb8(frames.data_ptr(), out.data_ptr(), n, H, W, wm.data_ptr(), wm.shape[0],
+                                            _hip.ptr(rows), float(alpha), cf, ws.data_ptr(), ws.numel(), _hip.current_stream(),
+                                            self._o(min(cf, n) * H * W * 3)))
         return out
 
     def detect(self, frames, L, alpha=20, want_bits=False, counts=None):
@@ -336,14 +320,10 @@ class DctEngine:
         bits = t.empty((n, N), dtype=t.uint8, device=self.device) if want_bits else None
         cf = self._chunk(n, H, W)
         ws = self.workspace(H, W, cf)
-        stream = _hip.current_stream()
-        fused = not (self.opts is not None and self.opts.flags & _hip.F_SEPARATE_DETECT)
-
-        def launch(o):
-            _hip.check(self.lib.ofmk_embed_detect_rgb8(frames.data_ptr(), out.data_ptr(), n, H, W, wm.data_ptr(),
-                                                       wm.shape[0], _hip.ptr(rows), float(alpha), int(L),
-                                                       counts.data_ptr(), _hip.ptr(bits), cf, ws.data_ptr(), ws.numel(), stream, o))
-        self._launch_marking(launch, frames, out, min(cf, n) * H * W * 3, fused, chunks=-(-n // cf))
+        _hip.check(self.lib.ofmk_embed_detect_rgb8(frames.data_ptr(), out.data_ptr(), n, H, W, wm.data_ptr(),
+                                                   wm.shape[0], _hip.ptr(rows), float(alpha), int(L),
+                                                   counts.data_ptr(), _hip.ptr(bits), cf, ws.data_ptr(), ws.numel(),
+                                                   _hip.current_stream(), self._o(min(cf, n) * H * W * 3)))
         return out, counts, bits
 
     def payloads(self, counts, n_bits: int, perm, out=None, counts_out=None):
@@ -508,7 +488,6 @@ class DctEngine:
         per-workgroup form [n, tiles, L] the frame kernel stores in full -- no fill dispatch in front of it
         (include/offmark_hip.h: OFMK_F_PARTIAL_COUNTS; L <= 2048); hand it to payloads() / counts_from_partial().
         ``copies``: one such buffer per copy, [copies, n, ...].  Returns (counts, the flag for the call's opts)."""
-        t = self.torch
         shape, flag = (n, int(L)), 0
         if partial:
             tiles = int(self.lib.ofmk_svd_count_tiles(H, W, int(blk)))
@@ -517,12 +496,7 @@ class DctEngine:
             shape, flag = (n, tiles, int(L)), _hip.F_PARTIAL_COUNTS
         if copies is not None:
             shape = (copies,) + shape
-        if counts is None:
-            counts = t.empty(shape, dtype=t.int32, device=self.device)
-        elif not (isinstance(counts, t.Tensor) and counts.is_cuda and counts.device == self.device and counts.dtype == t.int32
-                  and tuple(counts.shape) == shape and counts.is_contiguous()):
-            raise ValueError(f"counts must be a contiguous CUDA int32 tensor of shape {shape} on {self.device}")
-        return counts, flag
+        return self._buffer("counts", counts, shape, self.torch.int32, self.device), flag
 
     def svd_detect(self, frames, L, scale=15, want_bits=False, scales=None, blk=4, counts=None, partial=False):
         t = self.torch
@@ -621,12 +595,9 @@ class DctEngine:
         out = self._out(out, frames, (C, n, H, W, 3))
         cf = self._chunk(n, H, W)
         ws = self.workspace(H, W, cf)
-        stream = _hip.current_stream()
-
-        def launch(o):
-            _hip.check(self.lib.ofmk_embed_copies_rgb8(frames.data_ptr(), out.data_ptr(), C, n, H, W, wm.data_ptr(), wm.shape[0],
-                                                       _hip.ptr(rows), float(alpha), cf, ws.data_ptr(), ws.numel(), stream, o))
-        self._launch_marking(launch, frames, out, min(cf, n) * H * W * 3, False, chunks=-(-n // cf))
+        _hip.check(self.lib.ofmk_embed_copies_rgb8(frames.data_ptr(), out.data_ptr(), C, n, H, W, wm.data_ptr(), wm.shape[0],
+                                                   _hip.ptr(rows), float(alpha), cf, ws.data_ptr(), ws.numel(), _hip.current_stream(),
+                                                   self._o(min(cf, n) * H * W * 3)))
         return out
 
     def embed_detect_copies(self, frames, wm, wm_rows, L, alpha=20, out=None, want_bits=False, counts=None, copies=None, soft=None):
@@ -648,24 +619,18 @@ class DctEngine:
         cf = self._chunk(n, H, W)
         ws = self.copies_workspace(H, W, cf, C)
         stream = _hip.current_stream()
-        fused = not (self.opts is not None and self.opts.flags & _hip.F_SEPARATE_DETECT)
-
-        want_soft = soft is not None and soft is not False
-        if want_soft:
-            soft = self._soft(soft, n, L, copies=C)
-
-        def launch(o):
-            if want_soft:
-                _hip.check(self.lib.ofmk_embed_detect_copies_soft_rgb8(frames.data_ptr(), out.data_ptr(), C, n, H, W, wm.data_ptr(),
-                                                                       wm.shape[0], _hip.ptr(rows), float(alpha), L, counts.data_ptr(),
-                                                                       _hip.ptr(bits), soft.data_ptr(), cf, ws.data_ptr(), ws.numel(),
-                                                                       stream, o))
-                return
+        o = self._o(min(cf, n) * H * W * 3)
+        if soft is None or soft is False:
             _hip.check(self.lib.ofmk_embed_detect_copies_rgb8(frames.data_ptr(), out.data_ptr(), C, n, H, W, wm.data_ptr(),
                                                               wm.shape[0], _hip.ptr(rows), float(alpha), L, counts.data_ptr(),
                                                               _hip.ptr(bits), cf, ws.data_ptr(), ws.numel(), stream, o))
-        self._launch_marking(launch, frames, out, min(cf, n) * H * W * 3, fused, chunks=-(-n // cf))
-        return (out, counts, bits, soft) if want_soft else (out, counts, bits)
+            return out, counts, bits
+        soft = self._soft(soft, n, L, copies=C)
+        _hip.check(self.lib.ofmk_embed_detect_copies_soft_rgb8(frames.data_ptr(), out.data_ptr(), C, n, H, W, wm.data_ptr(),
+                                                               wm.shape[0], _hip.ptr(rows), float(alpha), L, counts.data_ptr(),
+                                                               _hip.ptr(bits), soft.data_ptr(), cf, ws.data_ptr(), ws.numel(),
+                                                               stream, o))
+        return out, counts, bits, soft
 
     def svd_embed_copies(self, frames, wm, wm_rows, scale=15, scales=None, blk=4, out=None, L=None, want_bits=False, counts=None,
                          partial=False, copies=None, soft=None):
