@@ -202,6 +202,43 @@ int ofmk_svd_sync_scores_rgb8(const uint8_t *in, int n, int H, int W, const doub
                               void *stream, const ofmk_opts *opts);
 int ofmk_svd_detect_soft_window_rgb8(const uint8_t *in, int n, int H, int W, int py, int px, int canvas_cols, int base, int L,
                                      const double *scales, int blk, long long *soft, void *stream, const ofmk_opts *opts);
+/* ---- block-grid resync for the DCT codec (BUILD EXTENSION, not reference semantics) -----------------------------------------
+ * The same two calls for the DCT codec, on interleaved u8 RGB frames of any H, W >= 8.  This codec HAS a frame-global
+ * dependency: the luminance mask's frame mean.  A decoder takes masks and mean from the frame as received, so a phase is read
+ * exactly as ofmk_detect_soft_rgb8 reads the contiguous crop that holds the phase's full blocks, frame[py : py + 8*rows,
+ * px : px + 8*cols], rows = (H - py) / 8, cols = (W - px) / 8 -- with the mean of THAT crop.  The right phase therefore reads
+ * near, not at, +-2^14 per block (the leak's mean differs from the marked frame's; the marking itself moved the masks).
+ *
+ * ofmk_sync_workspace_bytes: scratch of the dense search for `frames_in_flight` frames (12 bytes per pixel origin and 64 sums
+ *   per frame); 0 on bad arguments (frames_in_flight < 1, H or W < 8, H*W >= 2^28).
+ *
+ * ofmk_sync_scores_rgb8: the dense phase search.
+ *   scores   device int64 [n][64]; scores[f][8*py + px] = sum over the blocks of that crop of |m|, m the per-block metric of
+ *            ofmk_detect_soft_rgb8(crop, alpha), integer for integer.  A phase without a full window scores 0.  Cleared by the
+ *            call whatever it held.  Divided by 2^14 * blocks, a marked grid scores near 0.99 and the other grids near 0.8
+ *            (C21 is a low-frequency coefficient: neighbouring phases correlate); offmark.resync.best_phase.
+ *   workspace / workspace_bytes / chunk_frames   as every DCT call, sized by ofmk_sync_workspace_bytes; frames go through in
+ *            chunks of min(chunk_frames, what fits, 65535).  OFMK_E_WORKSPACE below ofmk_sync_workspace_bytes(1, H, W).
+ *   Per chunk two launches: every pixel origin's 8x8 analysis and the 64 per-phase sums of the block DCs (timed as kind 0,
+ *   analyze), then every origin's metric under its phase's mean (kind 1, finalize).  One frame read, instead of 64 read-outs of
+ *   64 shifted copies.
+ *   OFMK_E_ARG before any HIP call: null pointers, n <= 0, H or W < 8, H*W >= 2^28, a nan / inf / non-positive alpha, unknown
+ *   flag bits, a null or misaligned workspace.
+ *
+ * ofmk_detect_soft_window_rgb8: the soft read-out of the blocks at phase (py, px), with the positions of a wider canvas.
+ *   py, px, canvas_cols, base, soft   as ofmk_svd_detect_soft_window_rgb8; read through the frame's own pitch (no copy)
+ *   workspace   of ofmk_workspace_bytes(frames_in_flight, 8*rows, 8*cols): the WINDOW's blocks
+ *   With py = px = 0, canvas_cols = W / 8, base = 0 and H, W multiples of 8 this is ofmk_detect_soft_rgb8, integer for integer.
+ *   Per chunk: the analyze kernel on the window (kind 0), the soft finalize with canvas positions (kind 1).
+ *   OFMK_E_ARG: the checks above, L < 1, a phase outside 0..7, no full unit at the phase, canvas_cols < cols, base < 0,
+ *   base + rows*canvas_cols >= 2^31.
+ * Both allocate nothing, synchronise nothing and are graph capturable; the tile-order flags are ignored. */
+size_t ofmk_sync_workspace_bytes(int frames_in_flight, int H, int W);
+int ofmk_sync_scores_rgb8(const uint8_t *in, int n, int H, int W, double alpha, long long *scores,
+                          int chunk_frames, void *workspace, size_t workspace_bytes, void *stream, const ofmk_opts *opts);
+int ofmk_detect_soft_window_rgb8(const uint8_t *in, int n, int H, int W, int py, int px, int canvas_cols, int base, int L,
+                                 double alpha, long long *soft,
+                                 int chunk_frames, void *workspace, size_t workspace_bytes, void *stream, const ofmk_opts *opts);
 /* ---- C differently marked copies of the same frames in one pass (the A/B workflow) ----------------------------------
  * tests/mark_video_to_hls.py:331-342 decodes every segment once per copy and marks it with payload segment(4b)||copy(4b).
  * These calls read the frames once, do the part of the codec that does not depend on the watermark bit once (DCT: analyze's

@@ -48,6 +48,7 @@
 #include "copies_kernels.hiph"
 #include "planar_copies_kernels.hiph"
 #include "resync_kernels.hiph"
+#include "dct_resync_kernels.hiph"
 
 namespace {
 
@@ -1165,6 +1166,99 @@ int embed_detect_copies_frames(const FrameFmt &f, const uint8_t *in, uint8_t *ou
     return launch_copy_fringe_copies(in, out, copies, n, f.H, f.W, cx.s);      // as in embed_copies_frames
 }
 
+// ---- block-grid resync of the DCT codec (dct_resync_kernels.hiph; build extension, not reference semantics) -------------------
+// Workspace of the dense phase search: per frame in flight one record (kRec floats) per pixel origin and the 64 per-phase sums.
+struct SyncWorkspace {
+    float *rec;                  // kRec planes of [frames][norig]
+    unsigned long long *sums;    // [frames][64]
+    int frames;                  // chunk capacity
+    size_t norig;
+};
+size_t sync_per_frame_bytes(int H, int W) { return (size_t)(H - 7) * (W - 7) * kRec * sizeof(float) + 64 * sizeof(unsigned long long); }
+
+int carve_sync(void *ws, size_t bytes, int H, int W, int want_frames, SyncWorkspace &out) {
+    if (!ws) return fail(OFMK_E_ARG, "workspace is null%s");
+    if ((uintptr_t)ws % 256) return fail(OFMK_E_ARG, "workspace must be 256-byte aligned%s");
+    const size_t per = sync_per_frame_bytes(H, W);
+    if (bytes < per + kFixedBytes) return fail(OFMK_E_WORKSPACE, "workspace smaller than ofmk_sync_workspace_bytes(1, H, W)%s");
+    size_t cap = (bytes - kFixedBytes) / per;
+    if (want_frames > 0 && (size_t)want_frames < cap) cap = want_frames;
+    if (cap > (size_t)kMaxChunk) cap = kMaxChunk;
+    out.frames = (int)cap;
+    out.norig = (size_t)(H - 7) * (W - 7);
+    out.rec = static_cast<float *>(ws);
+    out.sums = reinterpret_cast<unsigned long long *>(static_cast<char *>(ws) + align256(cap * out.norig * kRec * sizeof(float)));
+    return OFMK_OK;
+}
+
+int check_alpha(double alpha) {
+    if (!(alpha > 0.0) || !(alpha <= 1.79769313486231570815e308)) return fail(OFMK_E_ARG, "alpha must be a positive finite number%s");
+    return OFMK_OK;
+}
+
+// The dense phase search of frames [f0, f0 + cf): clear the chunk's per-phase sums, analyse every origin (timed as analyze),
+// score every origin under its phase's mean (timed as finalize).
+int sync_scores_chunk(const uint8_t *in, int f0, int cf, int H, int W, double alpha, long long *scores, const SyncWorkspace &ws,
+                      const Ctx &cx) {
+    DctSyncGeom g;
+    g.H = H;
+    g.W = W;
+    g.ow = W - 7;
+    g.rects_x = (W - 7 + kDsRect * kDsStrip - 1) / (kDsRect * kDsStrip);
+    g.frame_stride = (size_t)H * W * 3;
+    g.norig = ws.norig;
+    g.plane = (size_t)ws.frames * ws.norig;
+    const dim3 grid((unsigned)(g.rects_x * ((H - 7 + kDsRect - 1) / kDsRect)), (unsigned)cf);
+    HIP_TRY(launch_zero(ws.sums, (size_t)cf * 64 * sizeof(unsigned long long), cx.s));
+    {
+        ScopedTiming timing(KIND_ANALYZE, cx);
+        OFMK_TIMED_LAUNCH(timing, dct_sync_analyze_rgb8_kernel, grid, dim3(kThreads), 0, cx.s, in + (size_t)f0 * g.frame_stride, g, ws.rec,
+                          ws.sums);
+    }
+    {
+        ScopedTiming timing(KIND_FINALIZE, cx);
+        OFMK_TIMED_LAUNCH(timing, dct_sync_scores_kernel, grid, dim3(kThreads), 0, cx.s, g, ws.rec, ws.sums, alpha,
+                          reinterpret_cast<unsigned long long *>(scores) + (size_t)f0 * 64);
+    }
+    HIP_TRY(hipGetLastError());
+    return OFMK_OK;
+}
+
+// The window read-out of frames [f0, f0 + cf): analyze_kernel on the window's geometry (kind analyze), then the soft finalize with
+// canvas positions (kind finalize).  ws was carved for the window's blocks (8 rows x 8 cols pixels).
+int soft_window_chunk(const uint8_t *in, int f0, int cf, int H, int W, int py, int px, int rows, int cols, int canvas_cols, int base,
+                      int L, double alpha, long long *soft, const Workspace &ws, const Ctx &cx) {
+    Geom g = make_geom(8 * rows, 8 * cols, ws, cf);      // the window's blocks ...
+    g.W = W;                                             // ... read through the frame's pitch and stride
+    g.frame_stride = (size_t)H * W * 3;
+    const uint8_t *first = in + (size_t)f0 * g.frame_stride + ((size_t)py * W + px) * 3;
+    {
+        ScopedTiming timing(KIND_ANALYZE, cx);
+        OFMK_TIMED_LAUNCH(timing, (analyze_kernel<SRC_RGB8, false>), xcd_grid(g.nblk, cf), dim3(kThreads), 0, cx.s,
+                          static_cast<const void *>(first), g, ws.rec, ws.ysum, static_cast<int32_t *>(nullptr), 0);
+    }
+    DctWindowArgs a;
+    a.rec = ws.rec;
+    a.plane = ws.plane;
+    a.ysum = ws.ysum;
+    a.tiles = ws.tiles;
+    a.nblk = g.nblk;
+    a.cols = cols;
+    a.canvas_cols = canvas_cols;
+    a.base = base;
+    a.L = L;
+    a.alpha = alpha;
+    a.soft = soft + (size_t)f0 * L;
+    {
+        const int per_wg = kThreads * kFinItems;
+        ScopedTiming timing(KIND_FINALIZE, cx);
+        OFMK_TIMED_LAUNCH(timing, finalize_soft_window_kernel, dim3((unsigned)((a.nblk + per_wg - 1) / per_wg), (unsigned)cf), dim3(kThreads),
+                          0, cx.s, a);
+    }
+    HIP_TRY(hipGetLastError());
+    return OFMK_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1376,6 +1470,52 @@ int ofmk_svd_detect_soft_window_rgb8(const uint8_t *in, int n, int H, int W, int
     });
     HIP_TRY(hipGetLastError());
     return OFMK_OK;
+}
+
+// Build extension, not reference semantics (dct_resync_kernels.hiph): scores[f][8 py + px] = sum of |soft metric| over the full 8x8
+// windows of frame f at grid phase (py, px), each phase under the frame mean of ITS crop; int64 [n][64], cleared here whatever it
+// held.  H, W: any values >= 8.
+size_t ofmk_sync_workspace_bytes(int frames_in_flight, int H, int W) {
+    if (frames_in_flight < 1 || H < 8 || W < 8 || (long long)H * W >= (1LL << 28)) return 0;
+    return sync_per_frame_bytes(H, W) * (size_t)frames_in_flight + kFixedBytes;
+}
+
+int ofmk_sync_scores_rgb8(const uint8_t *in, int n, int H, int W, double alpha, long long *scores, int chunk_frames, void *workspace,
+                          size_t workspace_bytes, void *stream, const ofmk_opts *opts) {
+    if (int orc = check_opts(opts)) return orc;
+    if (int rc = check_dims(n, H, W)) return rc;
+    if (!in || !scores) return fail(OFMK_E_ARG, "null pointer%s");
+    if (int rc = check_alpha(alpha)) return rc;
+    SyncWorkspace ws;
+    if (int rc = carve_sync(workspace, workspace_bytes, H, W, chunk_frames, ws)) return rc;
+    const Ctx cx = make_ctx(stream, opts);
+    HIP_TRY(launch_zero(scores, (size_t)n * 64 * sizeof(long long), cx.s));
+    return for_chunks(n, ws.frames, [&](int f0, int cf) { return sync_scores_chunk(in, f0, cf, H, W, alpha, scores, ws, cx); });
+}
+
+// Build extension, not reference semantics (dct_resync_kernels.hiph): the soft read-out of the blocks at grid phase (py, px) -- block
+// (i, j) is the 8x8 block at pixel (py + 8i, px + 8j) -- added into position (base + i * canvas_cols + j) mod L; int64 [n][L], cleared
+// here.  Masks and frame mean come from the window.  py = px = 0, canvas_cols = W / 8, base = 0 on frames with H, W multiples of
+// 8: ofmk_detect_soft_rgb8, integer for integer.
+int ofmk_detect_soft_window_rgb8(const uint8_t *in, int n, int H, int W, int py, int px, int canvas_cols, int base, int L, double alpha,
+                                 long long *soft, int chunk_frames, void *workspace, size_t workspace_bytes, void *stream,
+                                 const ofmk_opts *opts) {
+    if (int orc = check_opts(opts)) return orc;
+    if (int rc = check_soft_args(in, n, H, W, L, soft)) return rc;
+    if (int rc = check_alpha(alpha)) return rc;
+    if (py < 0 || py > 7 || px < 0 || px > 7) return fail(OFMK_E_ARG, "the phase (py, px) must be in 0..7%s");
+    const int rows = (H - py) / 8, cols = (W - px) / 8;
+    if (rows < 1 || cols < 1) return fail(OFMK_E_ARG, "no full 8x8 unit at this phase%s");
+    if (canvas_cols < cols) return fail(OFMK_E_ARG, "canvas_cols is smaller than the window's units per row%s");
+    if (base < 0) return fail(OFMK_E_ARG, "base must not be negative%s");
+    if ((long long)base + (long long)rows * canvas_cols >= (1LL << 31)) return fail(OFMK_E_ARG, "base + rows * canvas_cols must be < 2^31%s");
+    Workspace ws;
+    if (int rc = carve(workspace, workspace_bytes, 8 * rows, 8 * cols, chunk_frames, ws)) return rc;
+    const Ctx cx = make_ctx(stream, opts);
+    HIP_TRY(launch_zero(soft, (size_t)n * L * sizeof(long long), cx.s));
+    return for_chunks(n, ws.frames, [&](int f0, int cf) {
+        return soft_window_chunk(in, f0, cf, H, W, py, px, rows, cols, canvas_cols, base, L, alpha, soft, ws, cx);
+    });
 }
 
 int ofmk_svd_embed_detect_rgb8(const uint8_t *in, uint8_t *out, int n, int H, int W, const uint8_t *wm, int n_wm,

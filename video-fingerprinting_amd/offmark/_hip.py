@@ -55,6 +55,9 @@ SIGNATURES = {
     "ofmk_svd_detect_soft_rgb8": (_i32, [_vp, _i32, _i32, _i32, _i32, _dp, _i32, _vp, _vp, _op]),
     "ofmk_svd_sync_scores_rgb8": (_i32, [_vp, _i32, _i32, _i32, _dp, _i32, _vp, _vp, _op]),
     "ofmk_svd_detect_soft_window_rgb8": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _dp, _i32, _vp, _vp, _op]),
+    "ofmk_sync_workspace_bytes": (_sz, [_i32, _i32, _i32]),
+    "ofmk_sync_scores_rgb8": (_i32, [_vp, _i32, _i32, _i32, _f64, _vp, _i32, _vp, _sz, _vp, _op]),
+    "ofmk_detect_soft_window_rgb8": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _f64, _vp, _i32, _vp, _sz, _vp, _op]),
     "ofmk_svd_embed_detect_rgb8": (_i32, [_vp, _vp, _i32, _i32, _i32, _vp, _i32, _vp, _dp, _i32, _i32, _vp, _vp, _vp, _op]),
     "ofmk_embed_copies_rgb8": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _f64, _i32, _vp, _sz, _vp, _op]),
     "ofmk_svd_embed_copies_rgb8": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _dp, _i32, _i32, _vp, _vp, _vp,

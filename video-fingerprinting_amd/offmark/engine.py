@@ -106,6 +106,7 @@ class DctEngine:
         # clamp every entry into [0, n_wm) either way -- include/offmark_hip.h)
         self.debug_checks = os.environ.get("OFFMARK_DEBUG_CHECKS", "0") not in ("", "0")
         self._ws = {}
+        self._resync_ws = {}          # slot -> (frame size, buffer): sync_workspace() / detect_soft_window(), see _side_ws
 
     # -- scratch ------------------------------------------------------------------------------
     def workspace(self, H: int, W: int, frames: int):
@@ -306,6 +307,59 @@ class DctEngine:
         ws = self.workspace(H, W, cf)
         _hip.check(self.lib.ofmk_detect_soft_rgb8(frames.data_ptr(), n, H, W, int(L), float(alpha), soft.data_ptr(), cf,
                                                   ws.data_ptr(), ws.numel(), _hip.current_stream(), self._o()))
+        return soft
+
+    # -- block-grid resync of cropped frames (build extension, not reference semantics; offmark.resync) ------------------------
+    def _side_ws(self, slot, key, nbytes):
+        """A scratch buffer of the resync calls, cached per ``slot`` next to -- never in place of -- workspace()'s buffer: one
+        frame size per slot, only ever growing."""
+        held = self._resync_ws.get(slot)
+        if held is None or held[0] != key or held[1].numel() < nbytes:
+            held = (key, self.torch.empty(nbytes, dtype=self.torch.uint8, device=self.device))
+            self._resync_ws[slot] = held
+        return held[1]
+
+    def sync_workspace(self, H: int, W: int, frames: int):
+        """Scratch of sync_scores for `frames` frames in flight (ofmk_sync_workspace_bytes: one record per pixel origin).  A cache
+        of its own: the ordinary workspace() buffer is neither replaced nor freed."""
+        nbytes = self.lib.ofmk_sync_workspace_bytes(min(int(frames), _MAX_CHUNK_FRAMES), H, W)
+        if nbytes == 0:
+            raise _hip.HipError(f"bad frame size {H}x{W}")
+        return self._side_ws("sync", (H, W), nbytes)
+
+    def sync_scores(self, frames, alpha=20, scores=None):
+        """The dense phase search: int64 [n, 64], entry 8 * py + px = the sum of |block metric| over the full 8x8 windows of the
+        frame at grid phase (py, px), i.e. ``detect_soft(crop, blocks, alpha).abs().sum(1)`` of the contiguous crop that holds the
+        phase's blocks -- masks and frame mean taken from that crop -- integer for integer.  H and W are any values >= 8.
+        offmark.resync.best_phase reads it."""
+        t = self.torch
+        n, H, W = self._check_frames(frames, t.uint8)
+        scores = self._soft(scores, n, 64)
+        # 12 bytes per pixel origin against 3 per pixel: a quarter of the frame budget keeps the records at the frames' size
+        cf = balanced_chunk(n, max(1, (self.chunk_frames or default_chunk_frames(H, W)) // 4))
+        ws = self.sync_workspace(H, W, cf)
+        _hip.check(self.lib.ofmk_sync_scores_rgb8(frames.data_ptr(), n, H, W, float(alpha), scores.data_ptr(), cf, ws.data_ptr(),
+                                                  ws.numel(), _hip.current_stream(), self._o()))
+        return scores
+
+    def detect_soft_window(self, frames, L, phase, canvas_cols, base=0, alpha=20, soft=None):
+        """detect_soft of the blocks at grid ``phase`` = (py, px): block (i, j) is the 8x8 block at pixel (py + 8i, px + 8j) and
+        adds into position (base + i * canvas_cols + j) % L, the position it has in a frame ``canvas_cols`` blocks wide.  Masks
+        and frame mean come from the window.  int64 [n, L]."""
+        t = self.torch
+        n, H, W = self._check_frames(frames, t.uint8)
+        soft = self._soft(soft, n, L)
+        py, px = (int(v) for v in phase)
+        cf = self._chunk(n, H, W)
+        if 0 <= py <= 7 and 0 <= px <= 7 and H - py >= 8 and W - px >= 8:
+            h8, w8 = (H - py) // 8 * 8, (W - px) // 8 * 8
+            nbytes = self.lib.ofmk_workspace_bytes(min(cf, _MAX_CHUNK_FRAMES), h8, w8)
+            ws = self._side_ws("window", (h8, w8), nbytes)
+        else:
+            ws = self._side_ws("window", (8, 8), self.lib.ofmk_workspace_bytes(1, 8, 8))       # the library refuses the phase
+        _hip.check(self.lib.ofmk_detect_soft_window_rgb8(frames.data_ptr(), n, H, W, py, px, int(canvas_cols), int(base), int(L),
+                                                         float(alpha), soft.data_ptr(), cf, ws.data_ptr(), ws.numel(),
+                                                         _hip.current_stream(), self._o()))
         return soft
 
     def embed_detect(self, frames, wm, L, alpha=20, wm_row=None, out=None, want_bits=False, counts=None):

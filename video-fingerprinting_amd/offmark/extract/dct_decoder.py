@@ -57,6 +57,17 @@ class DctDecoder:
         """frames: CUDA uint8 [n, H, W, 3] -> soft sums int64 [n, L] on device (> 0 reads as 1)."""
         return self.engine.detect_soft(frames, payload_len, alpha=self.alpha)
 
+    # -- block-grid resync of cropped frames (build extension, not reference semantics; offmark.resync) --------------------------
+    def sync_scores_u8(self, frames):
+        """frames: CUDA uint8 [n, H, W, 3], any H, W >= 8 -> int64 [n, 64] on device: per grid phase 8 * py + px the sum of
+        |block metric| over the phase's full 8x8 windows, each phase under its own crop's frame mean (engine.sync_scores)."""
+        return self.engine.sync_scores(frames, alpha=self.alpha)
+
+    def decode_soft_window_u8(self, frames, L, phase, canvas_cols, base=0):
+        """The soft sums int64 [n, L] of the blocks at grid ``phase``, with the positions of a frame ``canvas_cols`` blocks wide
+        (engine.detect_soft_window)."""
+        return self.engine.detect_soft_window(frames, L, phase, canvas_cols, base=base, alpha=self.alpha)
+
     def decode_soft_planes_yuv420(self, planes, height, width, payload_len, layout="i420"):
         """planes: CUDA uint8 [n, 1.5*H*W] (I420 or NV12) -> soft sums int64 [n, L] on device."""
         return self.engine.detect_soft_yuv420(planes, height, width, payload_len, alpha=self.alpha, layout=layout)
