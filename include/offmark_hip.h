@@ -466,6 +466,72 @@ int ofmk_yuv420_to_rgb8(const uint8_t *yuv, uint8_t *rgb, int layout, int n, int
                         const ofmk_opts *opts);
 int ofmk_rgb8_to_yuv420(const uint8_t *rgb, uint8_t *yuv, int layout, int n, int H, int W, void *stream,
                         const ofmk_opts *opts);
+/* ---- block-grid resync on 4:2:0 planes: reading CROPPED planar frames (BUILD EXTENSION, not reference semantics) ---------------
+ * The four resync calls above for frames given as planes (layout and frame size as the yuv420 calls: 1.5*H*W bytes per frame,
+ * frames consecutive), both codecs, blk 4, YUV channel 1.  New here: H and W need only be EVEN and >= 8, not multiples of 8,
+ * and nothing is asked of any address (W = 84 has 42-byte I420 chroma rows; 10x14 frames lie 210 bytes apart).
+ *
+ * Only the 16 phases with EVEN py and px exist on planes:
+ *   1. a crop at even pixel offsets cuts sub-planes out of the marked planes, and the build-defined conversion replicates chroma
+ *      over its 2x2 cell, so yuv420_to_rgb(crop of planes) == crop of yuv420_to_rgb(planes), byte for byte: such leaks read
+ *      correctly with both codecs;
+ *   2. a crop at an odd offset cannot be made on 4:2:0 planes without resampling chroma by half a sample.  Done through RGB
+ *      (convert, crop at (11, 21), convert back) it destroys both codecs' marks, which live in U: measured with the oracle,
+ *      phase contrast 1.017 (DwtDctSvd) and 1.005 (DCT) against 1.30 and 1.11 at the even offsets.  A property of a chroma
+ *      mark under 4:2:0, not of the search.
+ * So the searches run one solver / one block analysis per even pixel origin, a quarter of the RGB searches', on 1.5 B/px read
+ * once and without an RGB intermediate, and every score entry with an odd py or px is 0.
+ *
+ * sub(py, px) below is the frame's sub-planes for the pixel window [py : py + 8*r, px : px + 8*c], r = (H - py) / 8,
+ * c = (W - px) / 8: a planar frame of 8r x 8c pixels, which the existing planar calls can read.
+ *
+ * ofmk_svd_sync_scores_yuv420: the dense phase search of the DwtDctSvd codec.
+ *   scores   device int64 [n][64], cleared by the call whatever it held.  For even py, even px, r >= 1 and c >= 1:
+ *            scores[f][8*py + px] = sum of |m| over the units of sub(py, px), m exactly the unit metric of
+ *            ofmk_svd_detect_soft_yuv420 (blk 4) on that sub-frame -- which is also entry 8*py + px of
+ *            ofmk_svd_sync_scores_rgb8 on the converted frame (fact 1).  Every other entry (odd phases, phases without a unit)
+ *            is 0 (fact 2).
+ *   OFMK_E_ARG before any HIP call: the checks of ofmk_svd_sync_scores_rgb8, an unknown layout, odd H or W.
+ *
+ * ofmk_svd_detect_soft_window_yuv420: the soft read-out of the units of sub(py, px), with the positions of a wider canvas.
+ *   py, px   0, 2, 4 or 6; unit (i, j) of sub(py, px) is added into position (base + i*canvas_cols + j) mod L; canvas_cols,
+ *            base, soft and the scales as ofmk_svd_detect_soft_window_rgb8; read through the frame's own pitch (no copy)
+ *   With py = px = 0, canvas_cols = W / 8, base = 0 and H, W multiples of 8 this is ofmk_svd_detect_soft_yuv420 (blk 4),
+ *   integer for integer.  OFMK_E_ARG: the checks of ofmk_svd_detect_soft_window_rgb8, an unknown layout, odd H or W, odd py or px.
+ * Both are timed as kind 4 (svd).
+ *
+ * ofmk_sync_workspace_bytes_yuv420: scratch of the DCT codec's planar search for `frames_in_flight` frames (12 bytes per even
+ *   pixel origin and 16 sums per frame: at most ofmk_sync_workspace_bytes of the same shape, about a quarter of it); 0 on bad
+ *   arguments (frames_in_flight < 1, H or W < 8 or odd, H*W >= 2^28).
+ *
+ * ofmk_sync_scores_yuv420: the dense phase search of the DCT codec.
+ *   scores   as above with m the per-block metric of ofmk_detect_soft_yuv420(sub(py, px), alpha): masks and the luminance
+ *            mask's frame mean come from that sub-frame, as ofmk_sync_scores_rgb8 takes them from each phase's crop.
+ *   workspace / workspace_bytes / chunk_frames   as ofmk_sync_scores_rgb8, sized by ofmk_sync_workspace_bytes_yuv420;
+ *            OFMK_E_WORKSPACE below ofmk_sync_workspace_bytes_yuv420(1, H, W).
+ *   Per chunk two launches: every even origin's 8x8 analysis and the 16 per-phase sums of the block DCs (timed as kind 5, planar
+ *   analyze), then every origin's metric under its phase's mean (kind 1, finalize).
+ *   OFMK_E_ARG before any HIP call: the checks of ofmk_sync_scores_rgb8, an unknown layout, odd H or W.
+ *
+ * ofmk_detect_soft_window_yuv420: the soft read-out of the blocks of sub(py, px), with the positions of a wider canvas.
+ *   py, px, canvas_cols, base, soft   as ofmk_svd_detect_soft_window_yuv420
+ *   workspace   of ofmk_workspace_bytes(frames_in_flight, 8*r, 8*c): the WINDOW's blocks
+ *   With py = px = 0, canvas_cols = W / 8, base = 0 and H, W multiples of 8 this is ofmk_detect_soft_yuv420, integer for integer.
+ *   Per chunk: the planar analyze on the window (kind 5), the soft finalize with canvas positions (kind 1).
+ *   OFMK_E_ARG: the checks of ofmk_detect_soft_window_rgb8, an unknown layout, odd H or W, odd py or px.
+ * All four allocate nothing, synchronise nothing, are graph capturable and launch at most 65535 frames at a time; the tile-order
+ * flags and OFMK_F_PARTIAL_COUNTS are ignored. */
+int ofmk_svd_sync_scores_yuv420(const uint8_t *in, int layout, int n, int H, int W, const double *scales, int blk,
+                                long long *scores, void *stream, const ofmk_opts *opts);
+int ofmk_svd_detect_soft_window_yuv420(const uint8_t *in, int layout, int n, int H, int W, int py, int px, int canvas_cols,
+                                       int base, int L, const double *scales, int blk, long long *soft, void *stream,
+                                       const ofmk_opts *opts);
+size_t ofmk_sync_workspace_bytes_yuv420(int frames_in_flight, int H, int W);
+int ofmk_sync_scores_yuv420(const uint8_t *in, int layout, int n, int H, int W, double alpha, long long *scores,
+                            int chunk_frames, void *workspace, size_t workspace_bytes, void *stream, const ofmk_opts *opts);
+int ofmk_detect_soft_window_yuv420(const uint8_t *in, int layout, int n, int H, int W, int py, int px, int canvas_cols,
+                                   int base, int L, double alpha, long long *soft,
+                                   int chunk_frames, void *workspace, size_t workspace_bytes, void *stream, const ofmk_opts *opts);
 
 /* ---- DeShuffler.degenerate's epilogue for a batch, on the device ---------------------------
  * src/offmark/degenerator/de_shuffler.py:17-22: mean of bits[i::L] (from `counts`), undo the key

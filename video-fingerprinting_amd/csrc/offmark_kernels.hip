@@ -49,6 +49,7 @@
 #include "planar_copies_kernels.hiph"
 #include "resync_kernels.hiph"
 #include "dct_resync_kernels.hiph"
+#include "planar_resync_kernels.hiph"
 
 namespace {
 
@@ -1259,6 +1260,131 @@ int soft_window_chunk(const uint8_t *in, int f0, int cf, int H, int W, int py, i
     return OFMK_OK;
 }
 
+// ---- block-grid resync on 4:2:0 planes (planar_resync_kernels.hiph; build extension, not reference semantics) -------------------
+// What the planar resync calls check on top of their RGB counterparts: a known layout and EVEN H and W.  No multiple of 8 and no
+// alignment: the kernels load bytes.
+int check_planar_resync(int layout, int H, int W) {
+    if (layout != OFMK_YUV_I420 && layout != OFMK_YUV_NV12) return fail(OFMK_E_ARG, "layout must be OFMK_YUV_I420 or OFMK_YUV_NV12%s");
+    if (H % 2 || W % 2) return fail(OFMK_E_ARG, "4:2:0 planes need even H and W%s");
+    return OFMK_OK;
+}
+
+// the window calls' checks (both codecs); rows / cols: the window's units
+int check_planar_window(int H, int W, int py, int px, int canvas_cols, int base, int &rows, int &cols) {
+    if (py < 0 || py > 7 || px < 0 || px > 7) return fail(OFMK_E_ARG, "the phase (py, px) must be in 0..7%s");
+    if (py % 2 || px % 2) return fail(OFMK_E_ARG, "an odd phase does not exist on 4:2:0 planes: py and px must be even%s");
+    rows = (H - py) / 8;
+    cols = (W - px) / 8;
+    if (rows < 1 || cols < 1) return fail(OFMK_E_ARG, "no full 8x8 unit at this phase%s");
+    if (canvas_cols < cols) return fail(OFMK_E_ARG, "canvas_cols is smaller than the window's units per row%s");
+    if (base < 0) return fail(OFMK_E_ARG, "base must not be negative%s");
+    if ((long long)base + (long long)rows * canvas_cols >= (1LL << 31)) return fail(OFMK_E_ARG, "base + rows * canvas_cols must be < 2^31%s");
+    return OFMK_OK;
+}
+
+PlaneGeom make_plane_geom(int layout, int H, int W) {
+    PlaneGeom p;
+    p.H = H;
+    p.W = W;
+    p.cpitch = layout == OFMK_YUV_I420 ? W / 2 : W;
+    p.cstep = layout == OFMK_YUV_I420 ? 1 : 2;
+    p.frame_stride = (size_t)H * W * 3 / 2;
+    p.u_off = (size_t)H * W;
+    p.v_off = layout == OFMK_YUV_I420 ? p.u_off + (size_t)H * W / 4 : p.u_off + 1;
+    return p;
+}
+
+PWinGeom make_window_geom(int layout, int H, int W, int rows, int cols, int frames) {
+    PWinGeom g;
+    g.p = make_plane_geom(layout, H, W);
+    g.wb = cols;
+    g.nblk = rows * cols;
+    g.inv_wb = 1.0f / (float)cols;
+    g.frames = frames;
+    return g;
+}
+
+// Workspace of the DCT codec's planar search: per frame in flight one record per EVEN pixel origin and the 16 per-phase sums.
+size_t psync_origins(int H, int W) { return (size_t)(H / 2 - 3) * (W / 2 - 3); }
+size_t psync_per_frame_bytes(int H, int W) { return psync_origins(H, W) * kRec * sizeof(float) + 16 * sizeof(unsigned long long); }
+
+int carve_psync(void *ws, size_t bytes, int H, int W, int want_frames, SyncWorkspace &out) {
+    if (!ws) return fail(OFMK_E_ARG, "workspace is null%s");
+    if ((uintptr_t)ws % 256) return fail(OFMK_E_ARG, "workspace must be 256-byte aligned%s");
+    const size_t per = psync_per_frame_bytes(H, W);
+    if (bytes < per + kFixedBytes) return fail(OFMK_E_WORKSPACE, "workspace smaller than ofmk_sync_workspace_bytes_yuv420(1, H, W)%s");
+    size_t cap = (bytes - kFixedBytes) / per;
+    if (want_frames > 0 && (size_t)want_frames < cap) cap = want_frames;
+    if (cap > (size_t)kMaxChunk) cap = kMaxChunk;
+    out.frames = (int)cap;
+    out.norig = psync_origins(H, W);
+    out.rec = static_cast<float *>(ws);
+    out.sums = reinterpret_cast<unsigned long long *>(static_cast<char *>(ws) + align256(cap * out.norig * kRec * sizeof(float)));
+    return OFMK_OK;
+}
+
+// The planar dense search of frames [f0, f0 + cf): clear the chunk's per-phase sums, analyse every even origin (timed as the
+// planar analyze), score every origin under its phase's mean (timed as finalize).
+int psync_scores_chunk(const uint8_t *in, int layout, int f0, int cf, int H, int W, double alpha, long long *scores,
+                       const SyncWorkspace &ws, const Ctx &cx) {
+    PDctSyncGeom g;
+    g.p = make_plane_geom(layout, H, W);
+    g.oh = H / 2 - 3;
+    g.ow = W / 2 - 3;
+    g.rects_x = (g.ow + kPdRectX * kPdStrip - 1) / (kPdRectX * kPdStrip);
+    g.norig = ws.norig;
+    g.plane = (size_t)ws.frames * ws.norig;
+    const dim3 grid((unsigned)(g.rects_x * ((g.oh + kPdRectY - 1) / kPdRectY)), (unsigned)cf);
+    HIP_TRY(launch_zero(ws.sums, (size_t)cf * 16 * sizeof(unsigned long long), cx.s));
+    {
+        ScopedTiming timing(KIND_PLANAR_ANALYZE, cx);
+        OFMK_TIMED_LAUNCH(timing, dct_sync_analyze_yuv420_kernel, grid, dim3(kThreads), 0, cx.s, in + (size_t)f0 * g.p.frame_stride, g,
+                          ws.rec, ws.sums);
+    }
+    {
+        ScopedTiming timing(KIND_FINALIZE, cx);
+        OFMK_TIMED_LAUNCH(timing, dct_sync_scores_yuv420_kernel, grid, dim3(kThreads), 0, cx.s, g, ws.rec, ws.sums, alpha,
+                          reinterpret_cast<unsigned long long *>(scores) + (size_t)f0 * 64);
+    }
+    HIP_TRY(hipGetLastError());
+    return OFMK_OK;
+}
+
+// The planar window read-out of frames [f0, f0 + cf): the planar analyze on the window (kind planar analyze), then the soft
+// finalize with canvas positions (kind finalize).  ws was carved for the window's blocks.  The analyze grid's x extent is the
+// tile count emit_block files the per-tile sums under, and it is ws.tiles (both are ceil(nblk / kThreads)).
+int psoft_window_chunk(const uint8_t *in, int layout, int f0, int cf, int H, int W, int py, int px, int rows, int cols, int canvas_cols,
+                       int base, int L, double alpha, long long *soft, const Workspace &ws, const Ctx &cx) {
+    const PWinGeom g = make_window_geom(layout, H, W, rows, cols, cf);
+    const dim3 grid = grid_2d(g.nblk, cf);
+    if ((int)grid.x != ws.tiles) return fail(OFMK_E_ARG, "internal: tile count of the launch and of the workspace differ%s");
+    {
+        ScopedTiming timing(KIND_PLANAR_ANALYZE, cx);
+        OFMK_TIMED_LAUNCH(timing, analyze_window_yuv420_kernel, grid, dim3(kThreads), 0, cx.s, in + (size_t)f0 * g.p.frame_stride, g, py, px,
+                          ws.plane, ws.rec, ws.ysum);
+    }
+    DctWindowArgs a;
+    a.rec = ws.rec;
+    a.plane = ws.plane;
+    a.ysum = ws.ysum;
+    a.tiles = ws.tiles;
+    a.nblk = g.nblk;
+    a.cols = cols;
+    a.canvas_cols = canvas_cols;
+    a.base = base;
+    a.L = L;
+    a.alpha = alpha;
+    a.soft = soft + (size_t)f0 * L;
+    {
+        const int per_wg = kThreads * kFinItems;
+        ScopedTiming timing(KIND_FINALIZE, cx);
+        OFMK_TIMED_LAUNCH(timing, finalize_soft_window_kernel, dim3((unsigned)((a.nblk + per_wg - 1) / per_wg), (unsigned)cf), dim3(kThreads),
+                          0, cx.s, a);
+    }
+    HIP_TRY(hipGetLastError());
+    return OFMK_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1871,6 +1997,106 @@ int ofmk_yuv420_to_rgb8(const uint8_t *yuv, uint8_t *rgb, int layout, int n, int
 
 int ofmk_rgb8_to_yuv420(const uint8_t *rgb, uint8_t *yuv, int layout, int n, int H, int W, void *stream, const ofmk_opts *opts) {
     return convert_yuv420(yuv, const_cast<uint8_t *>(rgb), false, layout, n, H, W, stream, opts);
+}
+
+// ---- block-grid resync on 4:2:0 planes (planar_resync_kernels.hiph; build extension, not reference semantics) -------------------
+// scores[f][8 py + px], even py and px with a full unit: the sum of |unit metric| of ofmk_svd_detect_soft_yuv420 (blk 4) on the
+// frame's sub-planes for the pixel window [py : py + 8r, px : px + 8c]; every other entry 0 (an odd crop offset does not exist on
+// 4:2:0 planes).  int64 [n][64], cleared here whatever it held.  H, W: even, >= 8; no alignment asked of `in`.
+int ofmk_svd_sync_scores_yuv420(const uint8_t *in, int layout, int n, int H, int W, const double *scales, int blk, long long *scores,
+                                void *stream, const ofmk_opts *opts) {
+    if (int orc = check_opts(opts)) return orc;
+    if (int rc = check_dims(n, H, W)) return rc;
+    if (!in || !scores) return fail(OFMK_E_ARG, "null pointer%s");
+    if (int rc = check_planar_resync(layout, H, W)) return rc;
+    SvdArgs a;
+    if (int rc = check_resync_scales(a, scales, blk, true)) return rc;
+    const Ctx cx = make_ctx(stream, opts);
+    HIP_TRY(launch_zero(scores, (size_t)n * 64 * sizeof(long long), cx.s));
+    PSyncGeom g;
+    g.p = make_plane_geom(layout, H, W);
+    g.Hc = H / 2;
+    g.Wc = W / 2;
+    g.rects_x = (g.Wc - 3 + kPsRect * kPsStrip - 1) / (kPsRect * kPsStrip);
+    g.scale = a.scales[1];
+    const unsigned rects = (unsigned)(g.rects_x * ((g.Hc - 3 + kPsRect - 1) / kPsRect));
+    for_chunks(n, kMaxChunk, [&](int f0, int cf) {
+        ScopedTiming timing(KIND_SVD, cx);
+        OFMK_TIMED_LAUNCH(timing, svd_sync_scores_yuv420_kernel, dim3(rects, (unsigned)cf), dim3(kThreads), 0, cx.s,
+                          in + (size_t)f0 * g.p.frame_stride, g, reinterpret_cast<unsigned long long *>(scores) + (size_t)f0 * 64);
+        return OFMK_OK;
+    });
+    HIP_TRY(hipGetLastError());
+    return OFMK_OK;
+}
+
+// The soft read-out of the units at the even phase (py, px), read through the frame's own pitch, added into position
+// (base + i * canvas_cols + j) mod L; int64 [n][L], cleared here.  py = px = 0, canvas_cols = W / 8, base = 0 on frames with H, W
+// multiples of 8: ofmk_svd_detect_soft_yuv420 (blk 4), integer for integer.  scales[1] <= 0: all zeros, as that call.
+int ofmk_svd_detect_soft_window_yuv420(const uint8_t *in, int layout, int n, int H, int W, int py, int px, int canvas_cols, int base, int L,
+                                       const double *scales, int blk, long long *soft, void *stream, const ofmk_opts *opts) {
+    if (int orc = check_opts(opts)) return orc;
+    if (int rc = check_soft_args(in, n, H, W, L, soft)) return rc;
+    if (int rc = check_planar_resync(layout, H, W)) return rc;
+    int rows, cols;
+    if (int rc = check_planar_window(H, W, py, px, canvas_cols, base, rows, cols)) return rc;
+    SvdArgs sa;
+    if (int rc = check_resync_scales(sa, scales, blk, false)) return rc;
+    const Ctx cx = make_ctx(stream, opts);
+    HIP_TRY(launch_zero(soft, (size_t)n * L * sizeof(long long), cx.s));
+    if (!(sa.scales[1] > 0.f)) return OFMK_OK;
+    for_chunks(n, kMaxChunk, [&](int f0, int cf) {
+        ScopedTiming timing(KIND_SVD, cx);
+        const PWinGeom g = make_window_geom(layout, H, W, rows, cols, cf);
+        const WindowArgs w{py, px, canvas_cols, base, L, sa.scales[1], soft + (size_t)f0 * L};
+        OFMK_TIMED_LAUNCH(timing, svd_soft_window_yuv420_kernel, xcd_grid(g.nblk, cf), dim3(kThreads), 0, cx.s,
+                          in + (size_t)f0 * g.p.frame_stride, g, w);
+        return OFMK_OK;
+    });
+    HIP_TRY(hipGetLastError());
+    return OFMK_OK;
+}
+
+// The DCT codec's planar search: scratch for `frames_in_flight` frames (12 bytes per EVEN pixel origin and 16 sums per frame).
+size_t ofmk_sync_workspace_bytes_yuv420(int frames_in_flight, int H, int W) {
+    if (frames_in_flight < 1 || H < 8 || W < 8 || H % 2 || W % 2 || (long long)H * W >= (1LL << 28)) return 0;
+    return psync_per_frame_bytes(H, W) * (size_t)frames_in_flight + kFixedBytes;
+}
+
+// scores[f][8 py + px], even py and px with a full block: the sum of |block metric| of ofmk_detect_soft_yuv420 on the frame's
+// sub-planes for the pixel window [py : py + 8r, px : px + 8c], masks and frame mean from that sub-frame; every other entry 0.
+int ofmk_sync_scores_yuv420(const uint8_t *in, int layout, int n, int H, int W, double alpha, long long *scores, int chunk_frames,
+                            void *workspace, size_t workspace_bytes, void *stream, const ofmk_opts *opts) {
+    if (int orc = check_opts(opts)) return orc;
+    if (int rc = check_dims(n, H, W)) return rc;
+    if (!in || !scores) return fail(OFMK_E_ARG, "null pointer%s");
+    if (int rc = check_planar_resync(layout, H, W)) return rc;
+    if (int rc = check_alpha(alpha)) return rc;
+    SyncWorkspace ws;
+    if (int rc = carve_psync(workspace, workspace_bytes, H, W, chunk_frames, ws)) return rc;
+    const Ctx cx = make_ctx(stream, opts);
+    HIP_TRY(launch_zero(scores, (size_t)n * 64 * sizeof(long long), cx.s));
+    return for_chunks(n, ws.frames, [&](int f0, int cf) { return psync_scores_chunk(in, layout, f0, cf, H, W, alpha, scores, ws, cx); });
+}
+
+// The soft read-out of the blocks at the even phase (py, px), with canvas positions; masks and frame mean come from the window.
+// py = px = 0, canvas_cols = W / 8, base = 0 on frames with H, W multiples of 8: ofmk_detect_soft_yuv420, integer for integer.
+int ofmk_detect_soft_window_yuv420(const uint8_t *in, int layout, int n, int H, int W, int py, int px, int canvas_cols, int base, int L,
+                                   double alpha, long long *soft, int chunk_frames, void *workspace, size_t workspace_bytes, void *stream,
+                                   const ofmk_opts *opts) {
+    if (int orc = check_opts(opts)) return orc;
+    if (int rc = check_soft_args(in, n, H, W, L, soft)) return rc;
+    if (int rc = check_planar_resync(layout, H, W)) return rc;
+    if (int rc = check_alpha(alpha)) return rc;
+    int rows, cols;
+    if (int rc = check_planar_window(H, W, py, px, canvas_cols, base, rows, cols)) return rc;
+    Workspace ws;
+    if (int rc = carve(workspace, workspace_bytes, 8 * rows, 8 * cols, chunk_frames, ws)) return rc;
+    const Ctx cx = make_ctx(stream, opts);
+    HIP_TRY(launch_zero(soft, (size_t)n * L * sizeof(long long), cx.s));
+    return for_chunks(n, ws.frames, [&](int f0, int cf) {
+        return psoft_window_chunk(in, layout, f0, cf, H, W, py, px, rows, cols, canvas_cols, base, L, alpha, soft, ws, cx);
+    });
 }
 
 int ofmk_probe_xcc(int32_t *xcc_of_workgroup, int n_workgroups, void *stream, const ofmk_opts *opts) {

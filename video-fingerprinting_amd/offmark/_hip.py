@@ -95,6 +95,12 @@ SIGNATURES = {
                                                     _vp, _sz, _vp, _op]),
     "ofmk_yuv420_to_rgb8": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _op]),
     "ofmk_rgb8_to_yuv420": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _op]),
+    "ofmk_svd_sync_scores_yuv420": (_i32, [_vp, _i32, _i32, _i32, _i32, _dp, _i32, _vp, _vp, _op]),
+    "ofmk_svd_detect_soft_window_yuv420": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _dp, _i32, _vp, _vp, _op]),
+    "ofmk_sync_workspace_bytes_yuv420": (_sz, [_i32, _i32, _i32]),
+    "ofmk_sync_scores_yuv420": (_i32, [_vp, _i32, _i32, _i32, _i32, _f64, _vp, _i32, _vp, _sz, _vp, _op]),
+    "ofmk_detect_soft_window_yuv420": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _f64, _vp, _i32, _vp, _sz, _vp,
+                                              _op]),
     "ofmk_probe_xcc": (_i32, [_vp, _i32, _vp, _op]),
     "ofmk_hbm_copy": (_i32, [_vp, _vp, _sz, _vp]),
     "ofmk_hbm_read": (_i32, [_vp, _sz, _vp, _vp]),

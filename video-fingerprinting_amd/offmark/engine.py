@@ -753,6 +753,83 @@ class DctEngine:
                                                         self._o()))
         return soft
 
+    # -- block-grid resync of cropped 4:2:0 planes (build extension, not reference semantics; blk 4, channel 1; offmark.resync) --
+    # Only the 16 phases with even py and px exist on planes: an odd crop offset would need chroma resampled by half a sample,
+    # which destroys a chroma mark (include/offmark_hip.h).  H and W need only be even and >= 8.
+    def _check_planar_even(self, planes, H, W):
+        t = self.torch
+        if H < 8 or W < 8 or H % 2 or W % 2:
+            raise ValueError("cropped 4:2:0 frames need even H and W of at least 8")
+        if not (isinstance(planes, t.Tensor) and planes.is_cuda and planes.dtype == t.uint8 and planes.dim() == 2
+                and planes.shape[1] == H * W * 3 // 2 and planes.is_contiguous()):
+            raise ValueError("planes must be a contiguous CUDA uint8 tensor [n, H*W*3/2] (I420: Y|U|V, NV12: Y|UV per frame)")
+        return planes.shape[0]
+
+    def svd_sync_scores_yuv420(self, planes, H, W, scale=15, scales=None, blk=4, layout="i420", scores=None):
+        """The dense phase search on planes: int64 [n, 64].  For even py and px, entry 8 * py + px = the sum of |unit metric| of
+        svd_detect_soft_yuv420 (blk 4) over the units of the frame's sub-planes for the pixel window [py:py + 8r, px:px + 8c],
+        r = (H - py) // 8, c = (W - px) // 8 -- the even entries of svd_sync_scores(yuv420_to_rgb(planes)), integer for integer.
+        Odd phases and phases without a unit are 0.  offmark.resync.best_phase(..., even_only=True) reads it."""
+        n = self._check_planar_even(planes, H, W)
+        scores = self._soft(scores, n, 64)
+        _hip.check(self.lib.ofmk_svd_sync_scores_yuv420(planes.data_ptr(), self._layout(layout), n, H, W, _hip.scales3(scale, scales),
+                                                        int(blk), scores.data_ptr(), _hip.current_stream(), self._o()))
+        return scores
+
+    def svd_detect_soft_window_yuv420(self, planes, H, W, L, phase, canvas_cols, base=0, scale=15, scales=None, blk=4, layout="i420",
+                                      soft=None):
+        """svd_detect_soft_yuv420 of the units at the even grid ``phase`` = (py, px): unit (i, j) is the 8x8 block at pixel
+        (py + 8i, px + 8j), read through the frame's own pitch, and adds into position (base + i * canvas_cols + j) % L.
+        int64 [n, L]."""
+        n = self._check_planar_even(planes, H, W)
+        soft = self._soft(soft, n, L)
+        py, px = phase
+        _hip.check(self.lib.ofmk_svd_detect_soft_window_yuv420(planes.data_ptr(), self._layout(layout), n, H, W, int(py), int(px),
+                                                               int(canvas_cols), int(base), int(L), _hip.scales3(scale, scales), int(blk),
+                                                               soft.data_ptr(), _hip.current_stream(), self._o()))
+        return soft
+
+    def sync_workspace_yuv420(self, H: int, W: int, frames: int):
+        """Scratch of sync_scores_yuv420 for `frames` frames in flight (ofmk_sync_workspace_bytes_yuv420: one record per even
+        pixel origin).  A cache of its own, as sync_workspace()."""
+        nbytes = self.lib.ofmk_sync_workspace_bytes_yuv420(min(int(frames), _MAX_CHUNK_FRAMES), H, W)
+        if nbytes == 0:
+            raise _hip.HipError(f"bad frame size {H}x{W}")
+        return self._side_ws("sync420", (H, W), nbytes)
+
+    def sync_scores_yuv420(self, planes, H, W, alpha=20, layout="i420", scores=None):
+        """The DCT codec's dense phase search on planes: int64 [n, 64].  For even py and px, entry 8 * py + px =
+        ``detect_soft_yuv420(sub, blocks, alpha).abs().sum(1)`` of the frame's sub-planes for the pixel window [py:py + 8r,
+        px:px + 8c] -- masks and frame mean taken from that sub-frame -- integer for integer, which is also that entry of
+        sync_scores(yuv420_to_rgb(planes)).  Odd phases and phases without a block are 0."""
+        n = self._check_planar_even(planes, H, W)
+        scores = self._soft(scores, n, 64)
+        # 3 bytes of records per pixel against 1.5 of planes: half the frame budget keeps the records at the frames' size
+        cf = balanced_chunk(n, max(1, (self.chunk_frames or default_chunk_frames(H, W)) // 2))
+        ws = self.sync_workspace_yuv420(H, W, cf)
+        _hip.check(self.lib.ofmk_sync_scores_yuv420(planes.data_ptr(), self._layout(layout), n, H, W, float(alpha), scores.data_ptr(), cf,
+                                                    ws.data_ptr(), ws.numel(), _hip.current_stream(), self._o()))
+        return scores
+
+    def detect_soft_window_yuv420(self, planes, H, W, L, phase, canvas_cols, base=0, alpha=20, layout="i420", soft=None):
+        """detect_soft_yuv420 of the blocks at the even grid ``phase`` = (py, px): block (i, j) is the 8x8 block at pixel
+        (py + 8i, px + 8j), read through the frame's own pitch, and adds into position (base + i * canvas_cols + j) % L.  Masks
+        and frame mean come from the window.  int64 [n, L]."""
+        n = self._check_planar_even(planes, H, W)
+        soft = self._soft(soft, n, L)
+        py, px = (int(v) for v in phase)
+        cf = self._chunk(n, H, W)
+        if 0 <= py <= 7 and 0 <= px <= 7 and H - py >= 8 and W - px >= 8:
+            h8, w8 = (H - py) // 8 * 8, (W - px) // 8 * 8
+            nbytes = self.lib.ofmk_workspace_bytes(min(cf, _MAX_CHUNK_FRAMES), h8, w8)
+            ws = self._side_ws("window420", (h8, w8), nbytes)
+        else:
+            ws = self._side_ws("window420", (8, 8), self.lib.ofmk_workspace_bytes(1, 8, 8))    # the library refuses the phase
+        _hip.check(self.lib.ofmk_detect_soft_window_yuv420(planes.data_ptr(), self._layout(layout), n, H, W, py, px, int(canvas_cols),
+                                                           int(base), int(L), float(alpha), soft.data_ptr(), cf, ws.data_ptr(), ws.numel(),
+                                                           _hip.current_stream(), self._o()))
+        return soft
+
     def svd_embed_detect_yuv420(self, planes, H, W, wm, L, scale=15, wm_row=None, out=None, want_bits=False, scales=None, blk=4,
                                 counts=None, partial=False, layout="i420"):
         """Mark and verify on planes; counts / bits are what a reader of the WRITTEN planes gets (== svd_detect_yuv420(out))."""

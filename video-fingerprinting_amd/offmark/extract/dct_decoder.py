@@ -68,6 +68,16 @@ class DctDecoder:
         (engine.detect_soft_window)."""
         return self.engine.detect_soft_window(frames, L, phase, canvas_cols, base=base, alpha=self.alpha)
 
+    def sync_scores_planes_yuv420(self, planes, height, width, layout="i420"):
+        """planes: CUDA uint8 [n, 1.5*H*W] (I420 or NV12), even H, W >= 8 -> int64 [n, 64] on device: sync_scores_u8's sums at the
+        phases with even py and px, 0 elsewhere -- an odd crop offset does not exist on 4:2:0 planes (engine.sync_scores_yuv420)."""
+        return self.engine.sync_scores_yuv420(planes, height, width, alpha=self.alpha, layout=layout)
+
+    def decode_soft_window_planes_yuv420(self, planes, height, width, L, phase, canvas_cols, base=0, layout="i420"):
+        """The soft sums int64 [n, L] of the blocks at the even grid ``phase``, with the positions of a frame ``canvas_cols`` blocks
+        wide (engine.detect_soft_window_yuv420)."""
+        return self.engine.detect_soft_window_yuv420(planes, height, width, L, phase, canvas_cols, base=base, alpha=self.alpha, layout=layout)
+
     def decode_soft_planes_yuv420(self, planes, height, width, payload_len, layout="i420"):
         """planes: CUDA uint8 [n, 1.5*H*W] (I420 or NV12) -> soft sums int64 [n, L] on device."""
         return self.engine.detect_soft_yuv420(planes, height, width, payload_len, alpha=self.alpha, layout=layout)

@@ -19,8 +19,18 @@ contrast is 1.183 there (1.187 on a second seed set, 1.197 on 136x200 cropped at
 1.005 on the unmarked sources cropped the same way.  That is lower than DwtDctSvd's 1.28-1.45: C21 is a low-frequency coefficient
 and neighbouring phases correlate -- a property of the codec.  ``best_phase``, ``align_segments`` and ``units_per_phase`` are the
 same for both codecs.
-``read_cropped_leak`` is the recipe end to end, with either decoder.  Rescaled leaks are a different problem (resampling) and not
-handled; neither are 4:2:0 planes and blk 8.
+``read_cropped_leak`` is the recipe end to end, with either decoder.
+4:2:0 PLANES (I420 / NV12) are read at EVEN crop offsets, without an RGB intermediate: ``read_cropped_leak_yuv420`` over the
+decoders' ``sync_scores_planes_yuv420`` / ``decode_soft_window_planes_yuv420`` and ``best_phase(..., even_only=True)``.  A crop at
+even pixel offsets cuts sub-planes out of the marked planes, and the build-defined conversion replicates chroma over its 2x2
+cell, so converting the cropped planes gives the crop of the converted frame byte for byte: on the test recipe marked through
+planes -> RGB -> oracle encoder -> planes and cropped at (10, 20) or (2, 6), both codecs return the right phase, base and copies,
+with contrast 1.30-1.33 (DwtDctSvd) and 1.106-1.115 (DCT) over the 16 even phases, against 1.003-1.012 on the unmarked sources.
+A crop at an ODD offset cannot exist on 4:2:0 planes without resampling chroma by half a sample, and that destroys a mark that
+lives in U: made through RGB (convert, crop at (11, 21), convert back) the same leak reads with contrast 1.017 / 1.005, wrong
+phase and wrong copies.  That is a property of a chroma mark under 4:2:0, not of the search, so on planes the 48 phases with an
+odd py or px score 0 and take no part.
+Rescaled leaks are a different problem (resampling) and not handled; neither is blk 8.
 """
 from __future__ import annotations
 
@@ -36,15 +46,19 @@ def units_per_phase(H: int, W: int) -> np.ndarray:
     return (r[:, None] * c[None, :]).reshape(64)
 
 
-def best_phase(scores, H: int, W: int) -> dict:
+def best_phase(scores, H: int, W: int, even_only: bool = False) -> dict:
     """scores: [64] or [n, 64] sums of |soft metric| per phase (rows are added) of H x W frames ->
     dict(phase=(py, px), normalised=float64 [64], contrast=top / second).  normalised = score / (2^14 * units * frames): about 1
     on the marked grid; phases without units are excluded (0 there).  No verdict: the caller judges ``contrast``, which is about
     1.0 on flat content (a flat frame carries no phase information) and inf when one phase at most has units or the
-    second-best scores 0."""
+    second-best scores 0.  ``even_only`` (4:2:0 planes): only the phases with even py and px take part -- in the ranking, in
+    ``contrast`` and in ``normalised`` (0 elsewhere)."""
     s = np.asarray(scores, dtype=np.int64).reshape(-1, 64)
     units = units_per_phase(H, W)
     have = units > 0
+    if even_only:
+        even = np.arange(8) % 2 == 0
+        have &= (even[:, None] & even[None, :]).reshape(64)
     if not have.any():
         raise ValueError(f"a {H}x{W} frame holds no 8x8 unit")
     norm = np.zeros(64, np.float64)
@@ -122,6 +136,28 @@ def read_cropped_leak(decoder, frames, segment_of_frame, canvas_width: int, cand
         raise ValueError("segment_of_frame needs one entry per frame")
     found = best_phase(_host(decoder.sync_scores_u8(frames[:max(1, int(search_frames))])), H, W)
     soft = _host(decoder.decode_soft_window_u8(frames, L, found["phase"], int(canvas_width) // 8, base=0)).astype(np.int64)
+    labels = sorted(set(seg.tolist()))
+    by_segment = np.stack([soft[seg == s].sum(axis=0) for s in labels])
+    cands = [candidates[s] for s in labels] if isinstance(candidates, dict) else list(candidates)
+    out = align_segments(by_segment, cands, key)
+    out.update(phase=found["phase"], contrast=found["contrast"], normalised=found["normalised"], segments=labels, soft_by_segment=by_segment)
+    return out
+
+
+def read_cropped_leak_yuv420(decoder, planes, height: int, width: int, segment_of_frame, canvas_width: int, candidates, key=0, L: int = 8,
+                             search_frames: int = 8, layout: str = "i420") -> dict:
+    """read_cropped_leak for a leak that arrives as 4:2:0 planes, cropped at EVEN pixel offsets (module docstring: an odd offset
+    cannot exist on planes).  decoder: a DwtDctSvdDecoder (blk 4) or a DctDecoder (anything with their sync_scores_planes_yuv420 /
+    decode_soft_window_planes_yuv420); planes: CUDA uint8 [n, 1.5 * height * width] in ``layout`` ("i420" / "nv12"), height and
+    width even and >= 8; the other arguments and the returned dict as read_cropped_leak.  The phase search ranks the 16 even
+    phases only (best_phase(..., even_only=True)); nothing is converted to RGB."""
+    n, H, W = int(planes.shape[0]), int(height), int(width)
+    seg = np.asarray(segment_of_frame).reshape(-1)
+    if seg.size != n:
+        raise ValueError("segment_of_frame needs one entry per frame")
+    found = best_phase(_host(decoder.sync_scores_planes_yuv420(planes[:max(1, int(search_frames))], H, W, layout=layout)), H, W, even_only=True)
+    soft = _host(decoder.decode_soft_window_planes_yuv420(planes, H, W, L, found["phase"], int(canvas_width) // 8, base=0,
+                                                          layout=layout)).astype(np.int64)
     labels = sorted(set(seg.tolist()))
     by_segment = np.stack([soft[seg == s].sum(axis=0) for s in labels])
     cands = [candidates[s] for s in labels] if isinstance(candidates, dict) else list(candidates)
