@@ -533,6 +533,56 @@ int ofmk_detect_soft_window_yuv420(const uint8_t *in, int layout, int n, int H, 
                                    int base, int L, double alpha, long long *soft,
                                    int chunk_frames, void *workspace, size_t workspace_bytes, void *stream, const ofmk_opts *opts);
 
+/* ---- reading RESCALED leaks: fixed-point warp, fused geometry search, fused read-out (BUILD EXTENSION) ------------------------
+ * A leak that was cropped and scaled has lost the 8x8 grid.  It is resampled back onto the marked frame's pixel grid (the CANVAS,
+ * H x W) with the inverse of the crop and scale, and the canvas units are read with the unit metric of ofmk_svd_detect_soft_rgb8;
+ * read in canvas coordinates, a unit has the uncropped frame's position, so no rotation is left to resolve.  Interleaved u8 RGB,
+ * blk 4, YUV channel 1.  The warp is defined in integers, so every implementation agrees byte for byte:
+ *
+ *   ofmk_warp {ay, by, ax, bx}, Q16.  Canvas row y reads the leak (h x w) at pos = ay*y + by (int64): y0 = pos >> 16 (floor),
+ *   fy = (pos >> 8) & 255; columns alike with ax, bx.  A pixel is INSIDE iff 0 <= y0 <= h-1 and 0 <= x0 <= w-1; the second taps
+ *   are min(y0+1, h-1), min(x0+1, w-1).  Per channel
+ *       v = ((256-fy)*((256-fx)*p00 + fx*p01) + fy*((256-fx)*p10 + fx*p11) + 32768) >> 16
+ *   and 0 outside.  a = 65536, b = 0 returns the frame; b = k << 16 the frame shifted by k pixels.
+ *   Required: 2^12 <= ay, ax <= 2^20 and |by|, |bx| <= 2^48 (pos then stays far inside int64), else OFMK_E_ARG.
+ *   A leak of h x w made from canvas rows top:top+ch (and columns alike) has ay = round(h/ch * 65536),
+ *   by = round(((0.5 - top) * h/ch - 0.5) * 65536): offmark.resync.warp_of_crop.
+ *   Canvas unit (i, j), i < H/8, j < W/8, COUNTS iff all 64 of its pixels are inside; the maps are monotone, so the counting units
+ *   form a rectangle [i0, i1) x [j0, j1).
+ *
+ * ofmk_warp_units: host only, no GPU call.  out = {i0, i1, j0, j1}, all 0 when no unit counts.  h, w, H, W >= 1 (a leak smaller
+ *   than a unit may still fill units when it is upscaled), h*w and H*W < 2^28.
+ * ofmk_warp_rgb8: out, device u8 [n][Hout][Wout][3], is the canvas rectangle whose top-left canvas pixel is (oy, ox); every byte
+ *   is written.  geom is HOST memory.  One launch per 65535 frames, not timed.  OFMK_E_ARG: null pointers, n <= 0, h or w < 1,
+ *   Hout or Wout < 1, a product >= 2^28, oy or ox outside [0, 2^28), the map's range.
+ * ofmk_svd_warp_scores_rgb8: the geometry search over a given candidate list.
+ *   cands    DEVICE memory, ofmk_warp [K] (an int64 [K][4] array)
+ *   scores   device int64 [n][K]; scores[f][k] = sum of |m| over the counting units of frame f warped by candidate k, m exactly
+ *            the unit metric ofmk_svd_detect_soft_rgb8 gives on the warped unit.  Cleared by the call whatever it held.  A
+ *            candidate without a counting unit scores 0, and so does one whose map is out of range (the list is not read on the
+ *            host).  Divided by 2^14 * counting units, the true geometry of a marked leak scores about 0.8 and a geometry with
+ *            one crop edge off by a pixel falls to the unmarked level (offmark.resync.best_geometry).
+ *   One thread per canvas unit and candidate forms the unit's 64 warped pixels in registers: no warped frame is written, one
+ *   launch for up to 65535 candidates x 65535 frames (candidates in gridDim.y, frames in gridDim.z, both chunked).
+ *   OFMK_E_ARG before any HIP call: null pointers, n <= 0, K < 1, h or w < 1, H or W < 8, a product >= 2^28, blk != 4, a nan / inf
+ *   scale, a positive scale below 1e-3, scales[1] <= 0, unknown flag bits.
+ * ofmk_svd_detect_soft_warp_rgb8: the soft read-out at one geometry (HOST memory).
+ *   soft     device int64 [n][L], cleared by the call; counting unit (i, j) adds m into position (i * (W/8) + j) mod L.
+ *            scales[1] <= 0 or no counting unit: all zeros.
+ *   Equal, integer for integer, to ofmk_warp_rgb8 of the counting rectangle (origin (8*i0, 8*j0)) followed by
+ *   ofmk_svd_detect_soft_window_rgb8 at phase (0, 0) with canvas_cols = W/8 and base = i0 * (W/8) + j0; at the identity on a frame
+ *   with H, W multiples of 8 it is ofmk_svd_detect_soft_rgb8.  OFMK_E_ARG: as above, L < 1, the map's range.
+ * The three device calls allocate nothing, synchronise nothing and are graph capturable; the fused ones are timed as kind 4
+ * (svd); OFMK_F_PARTIAL_COUNTS and the tile-order flags are ignored. */
+typedef struct ofmk_warp { int64_t ay, by, ax, bx; } ofmk_warp;
+int ofmk_warp_units(int h, int w, int H, int W, const ofmk_warp *geom, int out[4]);
+int ofmk_warp_rgb8(const uint8_t *in, int n, int h, int w, uint8_t *out, int Hout, int Wout, int oy, int ox,
+                   const ofmk_warp *geom, void *stream, const ofmk_opts *opts);
+int ofmk_svd_warp_scores_rgb8(const uint8_t *in, int n, int h, int w, int H, int W, const ofmk_warp *cands, int K,
+                              const double *scales, int blk, long long *scores, void *stream, const ofmk_opts *opts);
+int ofmk_svd_detect_soft_warp_rgb8(const uint8_t *in, int n, int h, int w, int H, int W, const ofmk_warp *geom, int L,
+                                   const double *scales, int blk, long long *soft, void *stream, const ofmk_opts *opts);
+
 /* ---- DeShuffler.degenerate's epilogue for a batch, on the device ---------------------------
  * src/offmark/degenerator/de_shuffler.py:17-22: mean of bits[i::L] (from `counts`), undo the key
  * permutation (`perm` = DeShuffler.payload_idx, device int32 [L]), threshold strictly above the

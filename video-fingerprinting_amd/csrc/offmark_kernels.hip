@@ -50,6 +50,7 @@
 #include "resync_kernels.hiph"
 #include "dct_resync_kernels.hiph"
 #include "planar_resync_kernels.hiph"
+#include "warp_kernels.hiph"
 
 namespace {
 
@@ -832,6 +833,46 @@ int check_resync_scales(SvdArgs &a, const double *scales, int blk, bool need_mar
     return OFMK_OK;
 }
 
+// ---- rescaled leaks (warp_kernels.hiph) -----------------------------------------------------------------------------------------
+static_assert(sizeof(WarpMap) == sizeof(ofmk_warp) && sizeof(ofmk_warp) == 32, "ofmk_warp is four int64");
+
+// a leak may be smaller than one unit: upscaled it can still fill canvas units
+int check_leak_dims(int h, int w) {
+    if (h < 1 || w < 1 || (long long)h * w >= (1LL << 28)) return fail(OFMK_E_ARG, "leak h, w must be positive with h*w < 2^28%s");
+    return OFMK_OK;
+}
+
+int check_warp_map(const ofmk_warp *geom, WarpMap &m) {
+    m.ay = geom->ay; m.by = geom->by; m.ax = geom->ax; m.bx = geom->bx;
+    if (!warp_map_ok(m)) return fail(OFMK_E_ARG, "ofmk_warp: ay, ax must be in [2^12, 2^20] and |by|, |bx| <= 2^48%s");
+    return OFMK_OK;
+}
+
+// Units [u0, u1) of one axis whose 8 pixels are inside a leak of `len` samples.  Both conditions are monotone in u (a > 0): the
+// first pixel's pos >= 0 holds from some unit on, the last pixel's sample <= len - 1 up to some unit.
+void warp_axis_units(long long a, long long b, int len, int units, int &u0, int &u1) {
+    int lo = 0, hi = units;
+    while (lo < hi) {
+        const int mid = lo + (hi - lo) / 2;
+        if (a * (8LL * mid) + b >= 0) hi = mid; else lo = mid + 1;
+    }
+    u0 = lo;
+    lo = 0; hi = units;
+    while (lo < hi) {
+        const int mid = lo + (hi - lo) / 2;
+        if (((a * (8LL * mid + 7) + b) >> 16) > (long long)(len - 1)) hi = mid; else lo = mid + 1;
+    }
+    u1 = lo;
+}
+
+void warp_rect(const WarpMap &m, int h, int w, int H, int W, int out[4]) {
+    int i0, i1, j0, j1;
+    warp_axis_units(m.ay, m.by, h, H / 8, i0, i1);
+    warp_axis_units(m.ax, m.bx, w, W / 8, j0, j1);
+    const bool any = i0 < i1 && j0 < j1;
+    out[0] = any ? i0 : 0; out[1] = any ? i1 : 0; out[2] = any ? j0 : 0; out[3] = any ? j1 : 0;
+}
+
 // ---- C marked copies of the same frames (copies_kernels.hiph) -------------------------------------------------------
 constexpr int kMaxCopies = 16;       // a payload's copy field has 4 bits (fingerprint.payload_for_segment)
 
@@ -1592,6 +1633,117 @@ int ofmk_svd_detect_soft_window_rgb8(const uint8_t *in, int n, int H, int W, int
         const WindowArgs w{py, px, canvas_cols, base, L, sa.scales[1], soft + (size_t)f0 * L};
         OFMK_TIMED_LAUNCH(timing, svd_soft_window_rgb8_kernel, xcd_grid(g.nblk, cf), dim3(kThreads), 0, cx.s,
                           in + (size_t)f0 * g.frame_stride, gc, w);
+        return OFMK_OK;
+    });
+    HIP_TRY(hipGetLastError());
+    return OFMK_OK;
+}
+
+// ---- rescaled leaks (warp_kernels.hiph; build extensions, not reference semantics) ---------------------------------------------
+// Host only: the counting rectangle of canvas units, out = {i0, i1, j0, j1}, all 0 when no unit counts.
+int ofmk_warp_units(int h, int w, int H, int W, const ofmk_warp *geom, int out[4]) {
+    if (!geom || !out) return fail(OFMK_E_ARG, "null pointer%s");
+    if (int rc = check_leak_dims(h, w)) return rc;
+    if (H < 1 || W < 1 || (long long)H * W >= (1LL << 28)) return fail(OFMK_E_ARG, "canvas H, W must be positive with H*W < 2^28%s");
+    WarpMap m;
+    if (int rc = check_warp_map(geom, m)) return rc;
+    warp_rect(m, h, w, H, W, out);
+    return OFMK_OK;
+}
+
+// The leak resampled onto the canvas rectangle [oy, oy + Hout) x [ox, ox + Wout): u8 [n][Hout][Wout][3], every byte written.
+int ofmk_warp_rgb8(const uint8_t *in, int n, int h, int w, uint8_t *out, int Hout, int Wout, int oy, int ox, const ofmk_warp *geom,
+                   void *stream, const ofmk_opts *opts) {
+    if (int orc = check_opts(opts)) return orc;
+    if (n <= 0) return fail(OFMK_E_ARG, "n must be positive%s");
+    if (!in || !out || !geom) return fail(OFMK_E_ARG, "null pointer%s");
+    if (int rc = check_leak_dims(h, w)) return rc;
+    if (Hout < 1 || Wout < 1 || (long long)Hout * Wout >= (1LL << 28)) return fail(OFMK_E_ARG, "Hout, Wout must be positive with Hout*Wout < 2^28%s");
+    if (oy < 0 || ox < 0 || oy >= (1 << 28) || ox >= (1 << 28)) return fail(OFMK_E_ARG, "oy, ox must be in [0, 2^28)%s");
+    WarpArgs a;
+    if (int rc = check_warp_map(geom, a.m)) return rc;
+    const Ctx cx = make_ctx(stream, opts);
+    a.h = h; a.w = w; a.Hout = Hout; a.Wout = Wout; a.oy = oy; a.ox = ox;
+    a.in_stride = (size_t)h * w * 3;
+    a.out_stride = (size_t)Hout * Wout * 3;
+    for_chunks(n, kMaxChunk, [&](int f0, int cf) {
+        hipLaunchKernelGGL(warp_rgb8_kernel, grid_2d(Hout * Wout, cf), dim3(kThreads), 0, cx.s, in + (size_t)f0 * a.in_stride,
+                           out + (size_t)f0 * a.out_stride, a);
+        return OFMK_OK;
+    });
+    HIP_TRY(hipGetLastError());
+    return OFMK_OK;
+}
+
+// scores[f][k] = sum of |unit metric| over the counting units of frame f warped by cands[k] (DEVICE memory, [K]); int64 [n][K],
+// cleared here whatever it held.  Candidates sit in gridDim.y and frames in gridDim.z, both in chunks of at most 65535.
+int ofmk_svd_warp_scores_rgb8(const uint8_t *in, int n, int h, int w, int H, int W, const ofmk_warp *cands, int K, const double *scales,
+                              int blk, long long *scores, void *stream, const ofmk_opts *opts) {
+    if (int orc = check_opts(opts)) return orc;
+    if (int rc = check_dims(n, H, W)) return rc;
+    if (int rc = check_leak_dims(h, w)) return rc;
+    if (!in || !cands || !scores) return fail(OFMK_E_ARG, "null pointer%s");
+    if (K < 1) return fail(OFMK_E_ARG, "K must be at least 1%s");
+    if ((long long)n * K >= (1LL << 40)) return fail(OFMK_E_ARG, "n * K must be < 2^40%s");
+    SvdArgs sa;
+    if (int rc = check_resync_scales(sa, scales, blk, true)) return rc;
+    const Ctx cx = make_ctx(stream, opts);
+    HIP_TRY(launch_zero(scores, (size_t)n * K * sizeof(long long), cx.s));
+    WarpScoreArgs a;
+    a.h = h; a.w = w;
+    a.rows = H / 8; a.cols = W / 8;
+    a.tiles_x = (a.cols + kWarpTileW - 1) / kWarpTileW;
+    a.K = K;
+    a.frame_stride = (size_t)h * w * 3;
+    a.scale = sa.scales[1];
+    const long long tiles = (long long)a.tiles_x * ((a.rows + kWarpTileH - 1) / kWarpTileH);
+    const WarpMap *dc = reinterpret_cast<const WarpMap *>(cands);
+    for_chunks(K, kMaxChunk, [&](int k0, int ck) {
+        const long long room = (1LL << 30) / (tiles * ck);                       // workgroups per launch stay below 2^30
+        const int cap = room < 1 ? 1 : room > kMaxChunk ? kMaxChunk : (int)room;
+        return for_chunks(n, cap, [&](int f0, int cf) {
+            ScopedTiming timing(KIND_SVD, cx);
+            OFMK_TIMED_LAUNCH(timing, svd_warp_scores_rgb8_kernel, dim3((unsigned)tiles, (unsigned)ck, (unsigned)cf), dim3(kThreads), 0, cx.s,
+                              in + (size_t)f0 * a.frame_stride, dc + k0, a,
+                              reinterpret_cast<unsigned long long *>(scores) + (size_t)f0 * K + k0);
+            return OFMK_OK;
+        });
+    });
+    HIP_TRY(hipGetLastError());
+    return OFMK_OK;
+}
+
+// The soft read-out of the counting units of the leak warped by *geom (HOST memory), unit (i, j) into position (i * (W / 8) + j) mod L;
+// int64 [n][L], cleared here.  scales[1] <= 0 or no counting unit: all zeros.
+int ofmk_svd_detect_soft_warp_rgb8(const uint8_t *in, int n, int h, int w, int H, int W, const ofmk_warp *geom, int L, const double *scales,
+                                   int blk, long long *soft, void *stream, const ofmk_opts *opts) {
+    if (int orc = check_opts(opts)) return orc;
+    if (int rc = check_soft_args(in, n, H, W, L, soft)) return rc;
+    if (int rc = check_leak_dims(h, w)) return rc;
+    if (!geom) return fail(OFMK_E_ARG, "null pointer%s");
+    WarpReadArgs a;
+    if (int rc = check_warp_map(geom, a.m)) return rc;
+    SvdArgs sa;
+    if (int rc = check_resync_scales(sa, scales, blk, false)) return rc;
+    const Ctx cx = make_ctx(stream, opts);
+    HIP_TRY(launch_zero(soft, (size_t)n * L * sizeof(long long), cx.s));
+    int r[4];
+    warp_rect(a.m, h, w, H, W, r);
+    if (!(sa.scales[1] > 0.f) || r[1] == r[0]) return OFMK_OK;
+    a.h = h; a.w = w;
+    a.i0 = r[0]; a.j0 = r[2];
+    a.cols = r[3] - r[2];
+    a.nunits = (r[1] - r[0]) * a.cols;
+    a.canvas_cols = W / 8;
+    a.L = L;
+    a.frame_stride = (size_t)h * w * 3;
+    a.scale = sa.scales[1];
+    for_chunks(n, kMaxChunk, [&](int f0, int cf) {
+        ScopedTiming timing(KIND_SVD, cx);
+        WarpReadArgs ac = a;
+        ac.frames = cf;
+        ac.soft = soft + (size_t)f0 * L;
+        OFMK_TIMED_LAUNCH(timing, svd_soft_warp_rgb8_kernel, xcd_grid(a.nunits, cf), dim3(kThreads), 0, cx.s, in + (size_t)f0 * a.frame_stride, ac);
         return OFMK_OK;
     });
     HIP_TRY(hipGetLastError());

@@ -35,6 +35,14 @@ _vp, _i32, _f64, _sz, _u32 = C.c_void_p, C.c_int, C.c_double, C.c_size_t, C.c_ui
 _op = C.POINTER(Opts)
 _dp = C.POINTER(C.c_double)
 
+
+class Warp(C.Structure):
+    """ofmk_warp: the Q16 map canvas pixel -> leak sample of the rescaled-leak calls, pos = a * c + b per axis."""
+    _fields_ = [("ay", C.c_int64), ("by", C.c_int64), ("ax", C.c_int64), ("bx", C.c_int64)]
+
+
+_wp = C.POINTER(Warp)
+
 #: every symbol include/offmark_hip.h declares: name -> (restype, argtypes)
 SIGNATURES = {
     "ofmk_version": (_i32, []),
@@ -101,6 +109,10 @@ SIGNATURES = {
     "ofmk_sync_scores_yuv420": (_i32, [_vp, _i32, _i32, _i32, _i32, _f64, _vp, _i32, _vp, _sz, _vp, _op]),
     "ofmk_detect_soft_window_yuv420": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _f64, _vp, _i32, _vp, _sz, _vp,
                                               _op]),
+    "ofmk_warp_units": (_i32, [_i32, _i32, _i32, _i32, _wp, C.POINTER(_i32)]),
+    "ofmk_warp_rgb8": (_i32, [_vp, _i32, _i32, _i32, _vp, _i32, _i32, _i32, _i32, _wp, _vp, _op]),
+    "ofmk_svd_warp_scores_rgb8": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _dp, _i32, _vp, _vp, _op]),
+    "ofmk_svd_detect_soft_warp_rgb8": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _wp, _i32, _dp, _i32, _vp, _vp, _op]),
     "ofmk_probe_xcc": (_i32, [_vp, _i32, _vp, _op]),
     "ofmk_hbm_copy": (_i32, [_vp, _vp, _sz, _vp]),
     "ofmk_hbm_read": (_i32, [_vp, _sz, _vp, _vp]),

@@ -6,6 +6,7 @@ work on torch's current stream; nothing here synchronises.
 """
 from __future__ import annotations
 
+import ctypes as C
 import os
 import threading
 
@@ -593,6 +594,65 @@ class DctEngine:
         _hip.check(self.lib.ofmk_svd_detect_soft_window_rgb8(frames.data_ptr(), n, H, W, int(py), int(px), int(canvas_cols), int(base), int(L),
                                                              _hip.scales3(scale, scales), int(blk), soft.data_ptr(), _hip.current_stream(),
                                                              self._o()))
+        return soft
+
+    # -- rescaled leaks: fixed-point warp onto the marked frame's canvas (build extension; blk 4, channel 1; offmark.resync) -----
+    @staticmethod
+    def _warp_geom(geom):
+        g = [int(v) for v in np.asarray(geom).reshape(-1)]
+        if len(g) != 4:
+            raise ValueError("a warp geometry is (ay, by, ax, bx) in Q16")
+        return _hip.Warp(*g)
+
+    def warp(self, frames, geom, out_hw, origin=(0, 0), out=None):
+        """The leak ``frames`` (uint8 [n, h, w, 3]) resampled by ``geom`` = (ay, by, ax, bx) (Q16; offmark.resync.warp_of_crop) onto
+        the canvas rectangle of ``out_hw`` pixels whose top-left canvas pixel is ``origin``: uint8 [n, Hout, Wout, 3], 0 outside the
+        leak.  Integer bilinear (include/offmark_hip.h: ofmk_warp)."""
+        t = self.torch
+        n, h, w = self._check_frames(frames, t.uint8)
+        Hout, Wout = (int(v) for v in out_hw)
+        out = self._out(out, frames, (n, Hout, Wout, 3))
+        g = self._warp_geom(geom)
+        _hip.check(self.lib.ofmk_warp_rgb8(frames.data_ptr(), n, h, w, out.data_ptr(), Hout, Wout, int(origin[0]), int(origin[1]), C.byref(g),
+                                           _hip.current_stream(), self._o()))
+        return out
+
+    def warp_units(self, leak_hw, canvas_hw, geom):
+        """(i0, i1, j0, j1): the rectangle of canvas units whose 64 pixels all fall inside the leak under ``geom``; all 0 when none
+        does.  Host only."""
+        r = (C.c_int * 4)()
+        g = self._warp_geom(geom)
+        _hip.check(self.lib.ofmk_warp_units(int(leak_hw[0]), int(leak_hw[1]), int(canvas_hw[0]), int(canvas_hw[1]), C.byref(g), r))
+        return tuple(r)
+
+    def svd_warp_scores(self, frames, canvas_hw, cands, scale=15, scales=None, blk=4, scores=None):
+        """The geometry search over a candidate list: int64 [n, K], entry k = the sum of |unit metric| (svd_detect_soft's, blk 4)
+        over the counting units of the frame warped by cands[k].  ``cands``: int64 [K, 4] rows (ay, by, ax, bx), a tensor on this
+        device or an array (copied there).  No warped frame is written.  offmark.resync.best_geometry reads the result."""
+        t = self.torch
+        n, h, w = self._check_frames(frames, t.uint8)
+        if not isinstance(cands, t.Tensor):
+            cands = t.from_numpy(np.ascontiguousarray(np.asarray(cands, dtype=np.int64)))
+        cands = cands.to(device=self.device, dtype=t.int64).contiguous()
+        if cands.dim() != 2 or cands.shape[1] != 4 or cands.shape[0] < 1:
+            raise ValueError("cands must be int64 [K, 4] with K >= 1")
+        K = int(cands.shape[0])
+        scores = self._soft(scores, n, K)
+        _hip.check(self.lib.ofmk_svd_warp_scores_rgb8(frames.data_ptr(), n, h, w, int(canvas_hw[0]), int(canvas_hw[1]), cands.data_ptr(), K,
+                                                      _hip.scales3(scale, scales), int(blk), scores.data_ptr(), _hip.current_stream(),
+                                                      self._o()))
+        return scores
+
+    def svd_detect_soft_warp(self, frames, canvas_hw, geom, L, scale=15, scales=None, blk=4, soft=None):
+        """svd_detect_soft of the leak warped by ``geom`` onto a canvas of ``canvas_hw`` pixels, counting units only, unit (i, j) at
+        the position it has in the uncropped frame, (i * (W // 8) + j) % L.  int64 [n, L]; equals warp + svd_detect_soft_window."""
+        t = self.torch
+        n, h, w = self._check_frames(frames, t.uint8)
+        soft = self._soft(soft, n, L)
+        g = self._warp_geom(geom)
+        _hip.check(self.lib.ofmk_svd_detect_soft_warp_rgb8(frames.data_ptr(), n, h, w, int(canvas_hw[0]), int(canvas_hw[1]), C.byref(g), int(L),
+                                                           _hip.scales3(scale, scales), int(blk), soft.data_ptr(), _hip.current_stream(),
+                                                           self._o()))
         return soft
 
     def svd_embed_detect(self, frames, wm, L, scale=15, wm_row=None, out=None, want_bits=False, scales=None, blk=4, counts=None,

@@ -68,6 +68,19 @@ class DctDecoder:
         (engine.detect_soft_window)."""
         return self.engine.detect_soft_window(frames, L, phase, canvas_cols, base=base, alpha=self.alpha)
 
+    # -- rescaled leaks (build extension: offmark.resync.read_rescaled_leak at a KNOWN geometry; this codec has no search) ------
+    def decode_soft_warp_u8(self, frames, canvas_hw, geom, L):
+        """The soft sums int64 [n, L] of the leak warped by ``geom`` onto the canvas, with the uncropped frame's positions.  The
+        chain: engine.warp of the rectangle of counting units, then decode_soft_window_u8 at phase (0, 0) -- masks and frame mean
+        come from the warped rectangle, as the decoder treats any received frame.  Zeros when no unit counts."""
+        eng = self.engine
+        H, W = int(canvas_hw[0]), int(canvas_hw[1])
+        i0, i1, j0, j1 = eng.warp_units(frames.shape[1:3], (H, W), geom)
+        if i1 == i0:
+            return eng.torch.zeros((frames.shape[0], int(L)), dtype=eng.torch.int64, device=frames.device)
+        rect = eng.warp(frames, geom, (8 * (i1 - i0), 8 * (j1 - j0)), origin=(8 * i0, 8 * j0))
+        return eng.detect_soft_window(rect, L, (0, 0), W // 8, base=i0 * (W // 8) + j0, alpha=self.alpha)
+
     def sync_scores_planes_yuv420(self, planes, height, width, layout="i420"):
         """planes: CUDA uint8 [n, 1.5*H*W] (I420 or NV12), even H, W >= 8 -> int64 [n, 64] on device: sync_scores_u8's sums at the
         phases with even py and px, 0 elsewhere -- an odd crop offset does not exist on 4:2:0 planes (engine.sync_scores_yuv420)."""

@@ -61,6 +61,17 @@ class DwtDctSvdDecoder:
         (engine.svd_detect_soft_window)."""
         return self.engine.svd_detect_soft_window(frames, L, phase, canvas_cols, base=base, scales=self._scales, blk=self.blk)
 
+    # -- rescaled leaks (build extension; blk 4 only: offmark.resync.read_rescaled_leak) ----------------------------------------
+    def warp_scores_u8(self, frames, canvas_hw, cands):
+        """frames: CUDA uint8 [n, h, w, 3], the leak; cands: int64 [K, 4] warp geometries -> int64 [n, K] on device: per candidate
+        the sum of |unit metric| over the canvas units that fall inside the leak (engine.svd_warp_scores)."""
+        return self.engine.svd_warp_scores(frames, canvas_hw, cands, scales=self._scales, blk=self.blk)
+
+    def decode_soft_warp_u8(self, frames, canvas_hw, geom, L):
+        """The soft sums int64 [n, L] of the leak warped by ``geom`` onto the canvas, with the uncropped frame's positions
+        (engine.svd_detect_soft_warp)."""
+        return self.engine.svd_detect_soft_warp(frames, canvas_hw, geom, L, scales=self._scales, blk=self.blk)
+
     def sync_scores_planes_yuv420(self, planes, height, width, layout="i420"):
         """planes: CUDA uint8 [n, 1.5*H*W] (I420 or NV12), even H, W >= 8 -> int64 [n, 64] on device: sync_scores_u8's sums at the
         phases with even py and px, 0 elsewhere -- an odd crop offset does not exist on 4:2:0 planes (engine.svd_sync_scores_yuv420)."""

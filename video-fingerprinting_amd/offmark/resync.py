@@ -30,7 +30,15 @@ A crop at an ODD offset cannot exist on 4:2:0 planes without resampling chroma b
 lives in U: made through RGB (convert, crop at (11, 21), convert back) the same leak reads with contrast 1.017 / 1.005, wrong
 phase and wrong copies.  That is a property of a chroma mark under 4:2:0, not of the search, so on planes the 48 phases with an
 odd py or px score 0 and take no part.
-Rescaled leaks are a different problem (resampling) and not handled; neither is blk 8.
+RESCALED leaks (cropped and zoomed back, or re-encoded at another resolution; interleaved RGB) have lost the 8x8 grid.  They are
+resampled back onto the marked frame's pixel grid (the canvas) with the inverse of the crop and scale -- an integer bilinear warp,
+``warp_of_crop`` -- and the canvas units that fall wholly inside the leak (``warp_units``) are read with the same unit metric, at
+the positions they have in the uncropped frame: no rotation is left.  ``DwtDctSvdDecoder.warp_scores_u8`` scores a list of
+candidate geometries (``crop_candidates``) in one fused call, ``best_geometry`` ranks them, ``decode_soft_warp_u8`` (both decoders)
+reads at one geometry: ``read_rescaled_leak``.  The score is as sharp as the phase search -- one crop edge off by a pixel falls to
+the unmarked level, rows and columns do not separate -- and only DwtDctSvd has a search: the DCT codec's C21 is small on smooth
+resampled content whether marked or not, so it reads at a geometry known from the sizes or found by other means.
+Rotation, shear, 4:2:0 planes under a rescale and blk 8 are not handled.
 """
 from __future__ import annotations
 
@@ -77,14 +85,15 @@ def shuffled(payload, key) -> np.ndarray:
     return np.asarray(Shuffler(key=key).generate_wm(p, (p.size,))).reshape(-1)
 
 
-def align_segments(soft_by_segment, candidates, key) -> dict:
+def align_segments(soft_by_segment, candidates, key, bases=None) -> dict:
     """One rotation of the L payload positions, common to all segments, and per segment the candidate it then reads as.
     soft_by_segment: [S, L] soft sums read with base 0; candidates[s]: the payloads (L bits each) segment s may carry.
     With T[s][q] = soft[s][(q - base) % L], maximises over base in 0..L-1
         sum_s max_k sum_q (2 * shuffled(candidates[s][k])[q] - 1) * T[s][q]
     (integers, so ties are exact).  -> dict(base, picks int [S] (index into candidates[s]; the first on a tie), score,
     runner_up_score (the best other base's), ambiguous (another base, or another candidate of a segment at the best base, scores
-    the same))."""
+    the same)).  ``bases``: the rotations that take part (default: all L); (0,) for sums read in canvas coordinates, where no
+    rotation is left -- runner_up_score is then None."""
     soft = np.asarray(soft_by_segment, dtype=np.int64)
     if soft.ndim != 2 or len(candidates) != soft.shape[0]:
         raise ValueError("soft_by_segment must be [S, L] with one candidate list per segment")
@@ -95,24 +104,27 @@ def align_segments(soft_by_segment, candidates, key) -> dict:
         if c.shape[1] != L:
             raise ValueError(f"candidates of segment {s} are not {L} bits long")
         signs.append(c)
-    totals = np.empty(L, np.int64)
-    picks = np.empty((L, S), np.int64)
-    tied_pick = np.zeros(L, bool)
-    for base in range(L):
+    bases = list(range(L)) if bases is None else [int(b) % L for b in bases]
+    if not bases:
+        raise ValueError("bases must name at least one rotation")
+    totals = np.empty(len(bases), np.int64)
+    picks = np.empty((len(bases), S), np.int64)
+    tied_pick = np.zeros(len(bases), bool)
+    for b, base in enumerate(bases):
         T = np.roll(soft, base, axis=1)                    # T[s][q] = soft[s][(q - base) % L]
         total = 0
         for s in range(S):
             corr = signs[s] @ T[s]
             k = int(np.argmax(corr))
-            picks[base, s] = k
-            tied_pick[base] |= int((corr == corr[k]).sum()) > 1
+            picks[b, s] = k
+            tied_pick[b] |= int((corr == corr[k]).sum()) > 1
             total += int(corr[k])
-        totals[base] = total
+        totals[b] = total
     best = int(np.argmax(totals))
     others = np.delete(totals, best)
     runner_up = int(others.max()) if others.size else None
     ambiguous = bool(tied_pick[best] or (runner_up is not None and runner_up == int(totals[best])))
-    return dict(base=best, picks=picks[best].copy(), score=int(totals[best]), runner_up_score=runner_up, ambiguous=ambiguous)
+    return dict(base=bases[best], picks=picks[best].copy(), score=int(totals[best]), runner_up_score=runner_up, ambiguous=ambiguous)
 
 
 def _host(x) -> np.ndarray:
@@ -163,4 +175,124 @@ def read_cropped_leak_yuv420(decoder, planes, height: int, width: int, segment_o
     cands = [candidates[s] for s in labels] if isinstance(candidates, dict) else list(candidates)
     out = align_segments(by_segment, cands, key)
     out.update(phase=found["phase"], contrast=found["contrast"], normalised=found["normalised"], segments=labels, soft_by_segment=by_segment)
+    return out
+
+
+# ---- rescaled leaks: the warp onto the marked frame's canvas ------------------------------------------------------------------
+WARP_ONE = 1 << 16                     # the warp's fixed point (Q16)
+WARP_MIN_A, WARP_MAX_A = 1 << 12, 1 << 20
+
+
+def _round_div(num: int, den: int) -> int:
+    """round(num / den), halves up, in exact integers (den > 0)."""
+    return (2 * num + den) // (2 * den)
+
+
+def warp_of_crop(top: int, left: int, ch: int, cw: int, h: int, w: int) -> tuple:
+    """(ay, by, ax, bx), Q16: the map canvas pixel -> sample of a leak of h x w pixels that was made from canvas rows
+    top:top+ch and columns left:left+cw with half-pixel centres.  ay = round(h/ch * 2^16),
+    by = round(((0.5 - top) * h/ch - 0.5) * 2^16), columns alike; exact integer rounding, halves up."""
+    top, left, ch, cw, h, w = (int(v) for v in (top, left, ch, cw, h, w))
+    if ch < 1 or cw < 1 or h < 1 or w < 1:
+        raise ValueError("crop and leak sizes must be positive")
+    ay, ax = _round_div(h * WARP_ONE, ch), _round_div(w * WARP_ONE, cw)
+    by = _round_div(((1 - 2 * top) * h - ch) * (WARP_ONE // 2), ch)
+    bx = _round_div(((1 - 2 * left) * w - cw) * (WARP_ONE // 2), cw)
+    return ay, by, ax, bx
+
+
+def _axis_units(a: int, b: int, length: int, units: int) -> tuple:
+    u = np.arange(units, dtype=np.int64)
+    ok = (a * (8 * u) + b >= 0) & (((a * (8 * u + 7) + b) >> 16) <= length - 1)
+    idx = np.flatnonzero(ok)
+    return (int(idx[0]), int(idx[-1]) + 1) if idx.size else (0, 0)
+
+
+def warp_units(leak_hw, canvas_hw, geom) -> tuple:
+    """(i0, i1, j0, j1): the canvas units (i < H // 8, j < W // 8) whose 64 pixels all fall inside the leak under ``geom``
+    (0 <= pos >> 16 <= size - 1 on both axes); the maps are monotone, so they form a rectangle.  All 0 when none counts.
+    Equal to the library's ofmk_warp_units."""
+    ay, by, ax, bx = (int(v) for v in np.asarray(geom).reshape(-1))
+    if not (WARP_MIN_A <= ay <= WARP_MAX_A and WARP_MIN_A <= ax <= WARP_MAX_A):
+        raise ValueError("ay and ax must be in [2^12, 2^20]")
+    i0, i1 = _axis_units(ay, by, int(leak_hw[0]), int(canvas_hw[0]) // 8)
+    j0, j1 = _axis_units(ax, bx, int(leak_hw[1]), int(canvas_hw[1]) // 8)
+    return (i0, i1, j0, j1) if i1 > i0 and j1 > j0 else (0, 0, 0, 0)
+
+
+def crop_candidates(canvas_hw, leak_hw, tops, lefts, heights, widths) -> np.ndarray:
+    """int64 [K, 4]: warp_of_crop of every crop (top, left, height, width) of the four lists' product, in that nesting order, that
+    lies inside the canvas and whose scale is in the warp's range."""
+    H, W = int(canvas_hw[0]), int(canvas_hw[1])
+    h, w = int(leak_hw[0]), int(leak_hw[1])
+    out = []
+    for top in tops:
+        for left in lefts:
+            for ch in heights:
+                for cw in widths:
+                    if top < 0 or left < 0 or ch < 1 or cw < 1 or top + ch > H or left + cw > W:
+                        continue
+                    g = warp_of_crop(top, left, ch, cw, h, w)
+                    if WARP_MIN_A <= g[0] <= WARP_MAX_A and WARP_MIN_A <= g[2] <= WARP_MAX_A:
+                        out.append(g)
+    return np.asarray(out, dtype=np.int64).reshape(-1, 4)
+
+
+def best_geometry(scores, cands, leak_hw, canvas_hw) -> dict:
+    """scores: [K] or [n, K] sums of |soft metric| per candidate geometry (rows are added); cands: int64 [K, 4] ->
+    dict(index, geometry=(ay, by, ax, bx), normalised=float64 [K], contrast=top / second).  normalised = score / (2^14 * counting
+    units * frames): about 0.8 at a marked leak's true geometry (bilinear resampling twice costs the rest), the unmarked level
+    (0.6-0.7) elsewhere; candidates without a counting unit are excluded (0 there).  No verdict: the caller judges ``contrast``
+    (inf when one candidate at most has units or the second-best scores 0)."""
+    cands = np.asarray(cands, dtype=np.int64).reshape(-1, 4)
+    K = cands.shape[0]
+    s = np.asarray(scores, dtype=np.int64).reshape(-1, K)
+    units = np.empty(K, np.int64)
+    for k in range(K):
+        i0, i1, j0, j1 = warp_units(leak_hw, canvas_hw, cands[k])
+        units[k] = (i1 - i0) * (j1 - j0)
+    have = units > 0
+    if not have.any():
+        raise ValueError("no candidate geometry has a counting unit")
+    norm = np.zeros(K, np.float64)
+    norm[have] = s.sum(axis=0)[have] / (float(ONE) * units[have] * s.shape[0])
+    order = np.argsort(-np.where(have, norm, -1.0), kind="stable")
+    top = int(order[0])
+    second = float(norm[order[1]]) if have.sum() > 1 else 0.0
+    contrast = float(norm[top] / second) if second > 0 else float("inf")
+    return dict(index=top, geometry=tuple(int(v) for v in cands[top]), normalised=norm, contrast=contrast)
+
+
+def read_rescaled_leak(decoder, frames, segment_of_frame, canvas_hw, candidates, geometries, key=0, L: int = 8, search_frames: int = 8) -> dict:
+    """A rescaled (cropped and / or resized) leak's copy per segment.  decoder: a DwtDctSvdDecoder (blk 4) or a DctDecoder
+    (anything with their decode_soft_warp_u8); frames: CUDA uint8 [n, h, w, 3], the leak as it is; canvas_hw: the marked
+    (uncropped) frames' (H, W); candidates: per segment the payloads it may carry, as read_cropped_leak; geometries: int64 [K, 4]
+    warp geometries (crop_candidates / warp_of_crop).  With K > 1 the first ``search_frames`` frames are scored under every
+    geometry (decoder.warp_scores_u8: DwtDctSvdDecoder only -- ValueError otherwise) and best_geometry picks one; with K = 1
+    nothing is searched.  All frames are then read at that geometry, summed per segment, and each segment takes the candidate
+    that correlates best with the position rotation fixed at 0 (canvas coordinates leave none).  -> dict(geometry, index,
+    contrast, normalised (None, None without a search), segments, soft_by_segment, base (0), picks, score, runner_up_score
+    (None), ambiguous).  No verdict on ``contrast``."""
+    n = int(frames.shape[0])
+    leak_hw = (int(frames.shape[1]), int(frames.shape[2]))
+    canvas_hw = (int(canvas_hw[0]), int(canvas_hw[1]))
+    seg = np.asarray(segment_of_frame).reshape(-1)
+    if seg.size != n:
+        raise ValueError("segment_of_frame needs one entry per frame")
+    geoms = np.asarray(_host(geometries), dtype=np.int64).reshape(-1, 4)
+    if geoms.shape[0] < 1:
+        raise ValueError("geometries must hold at least one (ay, by, ax, bx)")
+    if geoms.shape[0] > 1:
+        if not hasattr(decoder, "warp_scores_u8"):
+            raise ValueError(f"{type(decoder).__name__} has no geometry search (warp_scores_u8): give the one known geometry")
+        found = best_geometry(_host(decoder.warp_scores_u8(frames[:max(1, int(search_frames))], canvas_hw, geoms)), geoms, leak_hw, canvas_hw)
+    else:
+        found = dict(index=0, geometry=tuple(int(v) for v in geoms[0]), normalised=None, contrast=None)
+    soft = _host(decoder.decode_soft_warp_u8(frames, canvas_hw, found["geometry"], L)).astype(np.int64)
+    labels = sorted(set(seg.tolist()))
+    by_segment = np.stack([soft[seg == s].sum(axis=0) for s in labels])
+    cands = [candidates[s] for s in labels] if isinstance(candidates, dict) else list(candidates)
+    out = align_segments(by_segment, cands, key, bases=(0,))
+    out.update(geometry=found["geometry"], index=found["index"], contrast=found["contrast"], normalised=found["normalised"], segments=labels,
+               soft_by_segment=by_segment)
     return out
