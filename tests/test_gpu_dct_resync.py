@@ -125,6 +125,33 @@ def test_chunks_of_two_frames_equal_one_chunk(eng, leak):
     assert torch.equal(scores(2), eng.sync_scores(dev))
 
 
+def test_small_frames_in_chunks_of_two_equal_the_librarys_own_chunking(eng):
+    """5 random frames of 23x37 -- no multiple of 8, a nonzero phase, a partial last chunk, frame offsets into the shared records --
+    with chunk_frames = 2 and with chunk_frames = 0 (one chunk: the workspace holds all five), each call on a workspace sized
+    for it."""
+    import torch
+    from offmark import _hip
+    n, H, W, L = 5, 23, 37, 8
+    g = torch.Generator(device="cuda").manual_seed(23)
+    dev = torch.randint(0, 256, (n, H, W, 3), dtype=torch.uint8, device="cuda", generator=g)
+    stream = _hip.current_stream()
+    rows, cols = (H - 5) // 8, (W - 3) // 8
+
+    def both(cf):
+        scores, soft = garbage(n, 64), garbage(n, L)
+        ws = torch.empty(eng.lib.ofmk_sync_workspace_bytes(cf or n, H, W), dtype=torch.uint8, device="cuda")
+        _hip.check(eng.lib.ofmk_sync_scores_rgb8(dev.data_ptr(), n, H, W, 20.0, scores.data_ptr(), cf, ws.data_ptr(), ws.numel(), stream, None))
+        wws = torch.empty(eng.lib.ofmk_workspace_bytes(cf or n, 8 * rows, 8 * cols), dtype=torch.uint8, device="cuda")
+        _hip.check(eng.lib.ofmk_detect_soft_window_rgb8(dev.data_ptr(), n, H, W, 5, 3, 7, 3, L, 20.0, soft.data_ptr(), cf, wws.data_ptr(),
+                                                        wws.numel(), stream, None))
+        torch.cuda.synchronize()                              # the workspaces go out of scope here
+        return scores, soft
+
+    (s2, w2), (s0, w0) = both(2), both(0)
+    assert torch.equal(s2, s0) and torch.equal(w2, w0)
+    assert s0.any() and w0.any()
+
+
 # ---- 3. the window read-out --------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("base", [0, 29])
 @pytest.mark.parametrize("phase", [(5, 3), (0, 0), (7, 7)])

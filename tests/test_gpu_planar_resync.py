@@ -229,6 +229,34 @@ def test_rows_past_the_launch_chunk_equal_the_call_on_the_tail(eng, codec):
     assert torch.equal(s_all[:3], head[0]) and torch.equal(w_all[:3], head[1])
 
 
+def test_small_planes_in_chunks_of_two_equal_the_librarys_own_chunking(eng):
+    """The DCT calls on 5 random I420 frames of 22x36 -- no multiple of 8, a nonzero phase, a partial last chunk, frame offsets
+    into the shared records -- with chunk_frames = 2 and with chunk_frames = 0 (one chunk: the workspace holds all five), each
+    call on a workspace sized for it."""
+    import torch
+    from offmark import _hip
+    n, H, W, L = 5, 22, 36, 8
+    g = torch.Generator(device="cuda").manual_seed(22)
+    dev = torch.randint(0, 256, (n, H * W * 3 // 2), dtype=torch.uint8, device="cuda", generator=g)
+    stream = _hip.current_stream()
+    rows, cols = (H - 2) // 8, (W - 6) // 8
+
+    def both(cf):
+        scores, soft = garbage(n, 64), garbage(n, L)
+        ws = torch.empty(eng.lib.ofmk_sync_workspace_bytes_yuv420(cf or n, H, W), dtype=torch.uint8, device="cuda")
+        _hip.check(eng.lib.ofmk_sync_scores_yuv420(dev.data_ptr(), 0, n, H, W, 20.0, scores.data_ptr(), cf, ws.data_ptr(), ws.numel(), stream,
+                                                   None))
+        wws = torch.empty(eng.lib.ofmk_workspace_bytes(cf or n, 8 * rows, 8 * cols), dtype=torch.uint8, device="cuda")
+        _hip.check(eng.lib.ofmk_detect_soft_window_yuv420(dev.data_ptr(), 0, n, H, W, 2, 6, 7, 3, L, 20.0, soft.data_ptr(), cf, wws.data_ptr(),
+                                                          wws.numel(), stream, None))
+        torch.cuda.synchronize()                              # the workspaces go out of scope here
+        return scores, soft
+
+    (s2, w2), (s0, w0) = both(2), both(0)
+    assert torch.equal(s2, s0) and torch.equal(w2, w0)
+    assert s0.any() and w0.any()
+
+
 # ---- 5. end to end on the device ----------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("layout", LAYOUTS)
 @pytest.mark.parametrize("codec", pr.CODECS)

@@ -823,8 +823,9 @@ int svd_detect_soft(int n, int H, int W, int L, const double *scales, long long 
     return OFMK_OK;
 }
 
-// ---- block-grid resync of cropped frames (resync_kernels.hiph; blk 4, channel 1, RGB) -------------------------------------------
-// The checks the two resync calls share on top of their own: blk 4 only, finite scales, and -- need_mark -- a marked channel 1.
+// ---- block-grid resync of cropped and rescaled frames, DwtDctSvd (blk 4, channel 1) ------------------------------------------------
+// The checks the DwtDctSvd resync and warp calls share on top of their own: blk 4 only, finite scales, and -- need_mark -- a marked
+// channel 1.
 int check_resync_scales(SvdArgs &a, const double *scales, int blk, bool need_mark) {
     if (blk != 4) return fail(OFMK_E_ARG, "the resync calls are for blk 4%s");
     memset(&a, 0, sizeof(a));
@@ -1208,28 +1209,42 @@ int embed_detect_copies_frames(const FrameFmt &f, const uint8_t *in, uint8_t *ou
     return launch_copy_fringe_copies(in, out, copies, n, f.H, f.W, cx.s);      // as in embed_copies_frames
 }
 
-// ---- block-grid resync of the DCT codec (dct_resync_kernels.hiph; build extension, not reference semantics) -------------------
-// Workspace of the dense phase search: per frame in flight one record (kRec floats) per pixel origin and the 64 per-phase sums.
-struct SyncWorkspace {
-    float *rec;                  // kRec planes of [frames][norig]
-    unsigned long long *sums;    // [frames][64]
-    int frames;                  // chunk capacity
-    size_t norig;
+// ---- block-grid resync of cropped leaks, both codecs (resync_kernels.hiph, dct_resync_kernels.hiph, planar_resync_kernels.hiph;
+// build extensions, not reference semantics) ---------------------------------------------------------------------------------
+// What the frames of a resync call are, as FrameFmt is for the DCT codec's call path: an entry point checks its own arguments,
+// makes this value and calls one of the four bodies below (svd_sync_scores, svd_soft_window, sync_scores, soft_window).  Only the
+// leaf launchers -- the functions that build a kernel's geometry and name the kernel -- ask which format they have.
+enum LeakKind { LEAK_RGB8, LEAK_YUV420 };
+struct LeakFmt {
+    LeakKind kind;
+    int layout;            // LEAK_YUV420: OFMK_YUV_I420 / OFMK_YUV_NV12
+    int H, W;              // any values >= 8; even on planes (check_leak)
+    size_t frame_bytes;
+    int phases;            // grid phases the search sums: all 64, or the 16 with even py and px on planes
 };
-size_t sync_per_frame_bytes(int H, int W) { return (size_t)(H - 7) * (W - 7) * kRec * sizeof(float) + 64 * sizeof(unsigned long long); }
+LeakFmt rgb8_leak(int H, int W) { return {LEAK_RGB8, 0, H, W, (size_t)H * W * 3, 64}; }
+LeakFmt yuv420_leak(int layout, int H, int W) { return {LEAK_YUV420, layout, H, W, (size_t)H * W * 3 / 2, 16}; }
 
-int carve_sync(void *ws, size_t bytes, int H, int W, int want_frames, SyncWorkspace &out) {
-    if (!ws) return fail(OFMK_E_ARG, "workspace is null%s");
-    if ((uintptr_t)ws % 256) return fail(OFMK_E_ARG, "workspace must be 256-byte aligned%s");
-    const size_t per = sync_per_frame_bytes(H, W);
-    if (bytes < per + kFixedBytes) return fail(OFMK_E_WORKSPACE, "workspace smaller than ofmk_sync_workspace_bytes(1, H, W)%s");
-    size_t cap = (bytes - kFixedBytes) / per;
-    if (want_frames > 0 && (size_t)want_frames < cap) cap = want_frames;
-    if (cap > (size_t)kMaxChunk) cap = kMaxChunk;
-    out.frames = (int)cap;
-    out.norig = (size_t)(H - 7) * (W - 7);
-    out.rec = static_cast<float *>(ws);
-    out.sums = reinterpret_cast<unsigned long long *>(static_cast<char *>(ws) + align256(cap * out.norig * kRec * sizeof(float)));
+// What planes ask on top of interleaved frames: a known layout and EVEN H and W.  No multiple of 8 and no alignment: the kernels
+// load bytes.
+int check_leak(const LeakFmt &f) {
+    if (f.kind != LEAK_YUV420) return OFMK_OK;
+    if (f.layout != OFMK_YUV_I420 && f.layout != OFMK_YUV_NV12) return fail(OFMK_E_ARG, "layout must be OFMK_YUV_I420 or OFMK_YUV_NV12%s");
+    if (f.H % 2 || f.W % 2) return fail(OFMK_E_ARG, "4:2:0 planes need even H and W%s");
+    return OFMK_OK;
+}
+
+// the window calls' checks (both codecs); rows / cols: the window's units
+int check_window(const LeakFmt &f, int py, int px, int canvas_cols, int base, int &rows, int &cols) {
+    if (py < 0 || py > 7 || px < 0 || px > 7) return fail(OFMK_E_ARG, "the phase (py, px) must be in 0..7%s");
+    if (f.kind == LEAK_YUV420 && (py % 2 || px % 2))
+        return fail(OFMK_E_ARG, "an odd phase does not exist on 4:2:0 planes: py and px must be even%s");
+    rows = (f.H - py) / 8;
+    cols = (f.W - px) / 8;
+    if (rows < 1 || cols < 1) return fail(OFMK_E_ARG, "no full 8x8 unit at this phase%s");
+    if (canvas_cols < cols) return fail(OFMK_E_ARG, "canvas_cols is smaller than the window's units per row%s");
+    if (base < 0) return fail(OFMK_E_ARG, "base must not be negative%s");
+    if ((long long)base + (long long)rows * canvas_cols >= (1LL << 31)) return fail(OFMK_E_ARG, "base + rows * canvas_cols must be < 2^31%s");
     return OFMK_OK;
 }
 
@@ -1238,106 +1253,21 @@ int check_alpha(double alpha) {
     return OFMK_OK;
 }
 
-// The dense phase search of frames [f0, f0 + cf): clear the chunk's per-phase sums, analyse every origin (timed as analyze),
-// score every origin under its phase's mean (timed as finalize).
-int sync_scores_chunk(const uint8_t *in, int f0, int cf, int H, int W, double alpha, long long *scores, const SyncWorkspace &ws,
-                      const Ctx &cx) {
-    DctSyncGeom g;
-    g.H = H;
-    g.W = W;
-    g.ow = W - 7;
-    g.rects_x = (W - 7 + kDsRect * kDsStrip - 1) / (kDsRect * kDsStrip);
-    g.frame_stride = (size_t)H * W * 3;
-    g.norig = ws.norig;
-    g.plane = (size_t)ws.frames * ws.norig;
-    const dim3 grid((unsigned)(g.rects_x * ((H - 7 + kDsRect - 1) / kDsRect)), (unsigned)cf);
-    HIP_TRY(launch_zero(ws.sums, (size_t)cf * 64 * sizeof(unsigned long long), cx.s));
-    {
-        ScopedTiming timing(KIND_ANALYZE, cx);
-        OFMK_TIMED_LAUNCH(timing, dct_sync_analyze_rgb8_kernel, grid, dim3(kThreads), 0, cx.s, in + (size_t)f0 * g.frame_stride, g, ws.rec,
-                          ws.sums);
-    }
-    {
-        ScopedTiming timing(KIND_FINALIZE, cx);
-        OFMK_TIMED_LAUNCH(timing, dct_sync_scores_kernel, grid, dim3(kThreads), 0, cx.s, g, ws.rec, ws.sums, alpha,
-                          reinterpret_cast<unsigned long long *>(scores) + (size_t)f0 * 64);
-    }
-    HIP_TRY(hipGetLastError());
-    return OFMK_OK;
-}
-
-// The window read-out of frames [f0, f0 + cf): analyze_kernel on the window's geometry (kind analyze), then the soft finalize with
-// canvas positions (kind finalize).  ws was carved for the window's blocks (8 rows x 8 cols pixels).
-int soft_window_chunk(const uint8_t *in, int f0, int cf, int H, int W, int py, int px, int rows, int cols, int canvas_cols, int base,
-                      int L, double alpha, long long *soft, const Workspace &ws, const Ctx &cx) {
-    Geom g = make_geom(8 * rows, 8 * cols, ws, cf);      // the window's blocks ...
-    g.W = W;                                             // ... read through the frame's pitch and stride
-    g.frame_stride = (size_t)H * W * 3;
-    const uint8_t *first = in + (size_t)f0 * g.frame_stride + ((size_t)py * W + px) * 3;
-    {
-        ScopedTiming timing(KIND_ANALYZE, cx);
-        OFMK_TIMED_LAUNCH(timing, (analyze_kernel<SRC_RGB8, false>), xcd_grid(g.nblk, cf), dim3(kThreads), 0, cx.s,
-                          static_cast<const void *>(first), g, ws.rec, ws.ysum, static_cast<int32_t *>(nullptr), 0);
-    }
-    DctWindowArgs a;
-    a.rec = ws.rec;
-    a.plane = ws.plane;
-    a.ysum = ws.ysum;
-    a.tiles = ws.tiles;
-    a.nblk = g.nblk;
-    a.cols = cols;
-    a.canvas_cols = canvas_cols;
-    a.base = base;
-    a.L = L;
-    a.alpha = alpha;
-    a.soft = soft + (size_t)f0 * L;
-    {
-        const int per_wg = kThreads * kFinItems;
-        ScopedTiming timing(KIND_FINALIZE, cx);
-        OFMK_TIMED_LAUNCH(timing, finalize_soft_window_kernel, dim3((unsigned)((a.nblk + per_wg - 1) / per_wg), (unsigned)cf), dim3(kThreads),
-                          0, cx.s, a);
-    }
-    HIP_TRY(hipGetLastError());
-    return OFMK_OK;
-}
-
-// ---- block-grid resync on 4:2:0 planes (planar_resync_kernels.hiph; build extension, not reference semantics) -------------------
-// What the planar resync calls check on top of their RGB counterparts: a known layout and EVEN H and W.  No multiple of 8 and no
-// alignment: the kernels load bytes.
-int check_planar_resync(int layout, int H, int W) {
-    if (layout != OFMK_YUV_I420 && layout != OFMK_YUV_NV12) return fail(OFMK_E_ARG, "layout must be OFMK_YUV_I420 or OFMK_YUV_NV12%s");
-    if (H % 2 || W % 2) return fail(OFMK_E_ARG, "4:2:0 planes need even H and W%s");
-    return OFMK_OK;
-}
-
-// the window calls' checks (both codecs); rows / cols: the window's units
-int check_planar_window(int H, int W, int py, int px, int canvas_cols, int base, int &rows, int &cols) {
-    if (py < 0 || py > 7 || px < 0 || px > 7) return fail(OFMK_E_ARG, "the phase (py, px) must be in 0..7%s");
-    if (py % 2 || px % 2) return fail(OFMK_E_ARG, "an odd phase does not exist on 4:2:0 planes: py and px must be even%s");
-    rows = (H - py) / 8;
-    cols = (W - px) / 8;
-    if (rows < 1 || cols < 1) return fail(OFMK_E_ARG, "no full 8x8 unit at this phase%s");
-    if (canvas_cols < cols) return fail(OFMK_E_ARG, "canvas_cols is smaller than the window's units per row%s");
-    if (base < 0) return fail(OFMK_E_ARG, "base must not be negative%s");
-    if ((long long)base + (long long)rows * canvas_cols >= (1LL << 31)) return fail(OFMK_E_ARG, "base + rows * canvas_cols must be < 2^31%s");
-    return OFMK_OK;
-}
-
-PlaneGeom make_plane_geom(int layout, int H, int W) {
+PlaneGeom make_plane_geom(const LeakFmt &f) {
     PlaneGeom p;
-    p.H = H;
-    p.W = W;
-    p.cpitch = layout == OFMK_YUV_I420 ? W / 2 : W;
-    p.cstep = layout == OFMK_YUV_I420 ? 1 : 2;
-    p.frame_stride = (size_t)H * W * 3 / 2;
-    p.u_off = (size_t)H * W;
-    p.v_off = layout == OFMK_YUV_I420 ? p.u_off + (size_t)H * W / 4 : p.u_off + 1;
+    p.H = f.H;
+    p.W = f.W;
+    p.cpitch = f.layout == OFMK_YUV_I420 ? f.W / 2 : f.W;
+    p.cstep = f.layout == OFMK_YUV_I420 ? 1 : 2;
+    p.frame_stride = f.frame_bytes;
+    p.u_off = (size_t)f.H * f.W;
+    p.v_off = f.layout == OFMK_YUV_I420 ? p.u_off + (size_t)f.H * f.W / 4 : p.u_off + 1;
     return p;
 }
 
-PWinGeom make_window_geom(int layout, int H, int W, int rows, int cols, int frames) {
+PWinGeom make_window_geom(const LeakFmt &f, int rows, int cols, int frames) {
     PWinGeom g;
-    g.p = make_plane_geom(layout, H, W);
+    g.p = make_plane_geom(f);
     g.wb = cols;
     g.nblk = rows * cols;
     g.inv_wb = 1.0f / (float)cols;
@@ -1345,86 +1275,231 @@ PWinGeom make_window_geom(int layout, int H, int W, int rows, int cols, int fram
     return g;
 }
 
-// Workspace of the DCT codec's planar search: per frame in flight one record per EVEN pixel origin and the 16 per-phase sums.
-size_t psync_origins(int H, int W) { return (size_t)(H / 2 - 3) * (W / 2 - 3); }
-size_t psync_per_frame_bytes(int H, int W) { return psync_origins(H, W) * kRec * sizeof(float) + 16 * sizeof(unsigned long long); }
+// -- DwtDctSvd: no workspace, one launch per chunk of at most kMaxChunk frames --
+// leaf: the phase scores of cf frames from `first` into `scores` ([cf][64])
+void launch_svd_sync_scores(const LeakFmt &f, const uint8_t *first, int cf, float scale, unsigned long long *scores, const Ctx &cx) {
+    ScopedTiming timing(KIND_SVD, cx);
+    if (f.kind == LEAK_YUV420) {
+        PSyncGeom g;
+        g.p = make_plane_geom(f);
+        g.Hc = f.H / 2;
+        g.Wc = f.W / 2;
+        g.rects_x = (g.Wc - 3 + kPsRect * kPsStrip - 1) / (kPsRect * kPsStrip);
+        g.scale = scale;
+        const unsigned rects = (unsigned)(g.rects_x * ((g.Hc - 3 + kPsRect - 1) / kPsRect));
+        OFMK_TIMED_LAUNCH(timing, svd_sync_scores_yuv420_kernel, dim3(rects, (unsigned)cf), dim3(kThreads), 0, cx.s, first, g, scores);
+        return;
+    }
+    SyncGeom g;
+    g.H = f.H;
+    g.W = f.W;
+    g.rects_x = (f.W - 7 + kSyncRect * kSyncStrip - 1) / (kSyncRect * kSyncStrip);
+    g.rects = g.rects_x * ((f.H - 7 + kSyncRect - 1) / kSyncRect);
+    g.frame_stride = f.frame_bytes;
+    g.scale = scale;
+    OFMK_TIMED_LAUNCH(timing, svd_sync_scores_rgb8_kernel, dim3((unsigned)g.rects, (unsigned)cf), dim3(kThreads), 0, cx.s, first, g, scores);
+}
 
-int carve_psync(void *ws, size_t bytes, int H, int W, int want_frames, SyncWorkspace &out) {
+// leaf: the window read-out of cf frames from `first`; w.soft is these frames' [cf][L]
+void launch_svd_soft_window(const LeakFmt &f, const uint8_t *first, int cf, int rows, int cols, const WindowArgs &w, const Ctx &cx) {
+    ScopedTiming timing(KIND_SVD, cx);
+    if (f.kind == LEAK_YUV420) {
+        const PWinGeom g = make_window_geom(f, rows, cols, cf);
+        OFMK_TIMED_LAUNCH(timing, svd_soft_window_yuv420_kernel, xcd_grid(g.nblk, cf), dim3(kThreads), 0, cx.s, first, g, w);
+        return;
+    }
+    Geom g = svd_geom(f.H, f.W);             // the frame's W and stride ...
+    g.wb = cols;                             // ... with the window's units
+    g.inv_wb = 1.0f / (float)cols;
+    g.nblk = rows * cols;
+    g.frames = cf;
+    OFMK_TIMED_LAUNCH(timing, svd_soft_window_rgb8_kernel, xcd_grid(g.nblk, cf), dim3(kThreads), 0, cx.s, first, g, w);
+}
+
+// in, scores: checked by the entry point
+int svd_sync_scores(const LeakFmt &f, const uint8_t *in, int n, const double *scales, int blk, long long *scores, void *stream,
+                    const ofmk_opts *opts) {
+    if (int rc = check_leak(f)) return rc;
+    SvdArgs a;
+    if (int rc = check_resync_scales(a, scales, blk, true)) return rc;
+    const Ctx cx = make_ctx(stream, opts);
+    HIP_TRY(launch_zero(scores, (size_t)n * 64 * sizeof(long long), cx.s));
+    for_chunks(n, kMaxChunk, [&](int f0, int cf) {
+        launch_svd_sync_scores(f, in + (size_t)f0 * f.frame_bytes, cf, a.scales[1], reinterpret_cast<unsigned long long *>(scores) + (size_t)f0 * 64,
+                               cx);
+        return OFMK_OK;
+    });
+    HIP_TRY(hipGetLastError());
+    return OFMK_OK;
+}
+
+// in, n, H, W, L, soft: checked by the entry point (check_soft_args)
+int svd_soft_window(const LeakFmt &f, const uint8_t *in, int n, int py, int px, int canvas_cols, int base, int L, const double *scales,
+                    int blk, long long *soft, void *stream, const ofmk_opts *opts) {
+    if (int rc = check_leak(f)) return rc;
+    int rows, cols;
+    if (int rc = check_window(f, py, px, canvas_cols, base, rows, cols)) return rc;
+    SvdArgs sa;
+    if (int rc = check_resync_scales(sa, scales, blk, false)) return rc;
+    const Ctx cx = make_ctx(stream, opts);
+    HIP_TRY(launch_zero(soft, (size_t)n * L * sizeof(long long), cx.s));
+    if (!(sa.scales[1] > 0.f)) return OFMK_OK;
+    for_chunks(n, kMaxChunk, [&](int f0, int cf) {
+        const WindowArgs w{py, px, canvas_cols, base, L, sa.scales[1], soft + (size_t)f0 * L};
+        launch_svd_soft_window(f, in + (size_t)f0 * f.frame_bytes, cf, rows, cols, w, cx);
+        return OFMK_OK;
+    });
+    HIP_TRY(hipGetLastError());
+    return OFMK_OK;
+}
+
+// -- the DCT codec: two passes over records in the caller's workspace, chunks of what it holds --
+// Workspace of the dense phase search: per frame in flight one record (kRec floats) per origin searched -- every pixel origin
+// of interleaved frames, every EVEN one of planes -- and the per-phase sums.
+struct SyncWorkspace {
+    float *rec;                  // kRec planes of [frames][norig]
+    unsigned long long *sums;    // [frames][phases]
+    int frames;                  // chunk capacity
+    size_t norig;
+};
+size_t sync_origins(const LeakFmt &f) {
+    return f.kind == LEAK_YUV420 ? (size_t)(f.H / 2 - 3) * (f.W / 2 - 3) : (size_t)(f.H - 7) * (f.W - 7);
+}
+size_t sync_per_frame_bytes(const LeakFmt &f) { return sync_origins(f) * kRec * sizeof(float) + f.phases * sizeof(unsigned long long); }
+
+int carve_sync(void *ws, size_t bytes, const LeakFmt &f, int want_frames, SyncWorkspace &out) {
     if (!ws) return fail(OFMK_E_ARG, "workspace is null%s");
     if ((uintptr_t)ws % 256) return fail(OFMK_E_ARG, "workspace must be 256-byte aligned%s");
-    const size_t per = psync_per_frame_bytes(H, W);
-    if (bytes < per + kFixedBytes) return fail(OFMK_E_WORKSPACE, "workspace smaller than ofmk_sync_workspace_bytes_yuv420(1, H, W)%s");
+    const size_t per = sync_per_frame_bytes(f);
+    if (bytes < per + kFixedBytes)
+        return fail(OFMK_E_WORKSPACE, "workspace smaller than %s(1, H, W)",
+                    f.kind == LEAK_YUV420 ? "ofmk_sync_workspace_bytes_yuv420" : "ofmk_sync_workspace_bytes");
     size_t cap = (bytes - kFixedBytes) / per;
     if (want_frames > 0 && (size_t)want_frames < cap) cap = want_frames;
     if (cap > (size_t)kMaxChunk) cap = kMaxChunk;
     out.frames = (int)cap;
-    out.norig = psync_origins(H, W);
+    out.norig = sync_origins(f);
     out.rec = static_cast<float *>(ws);
     out.sums = reinterpret_cast<unsigned long long *>(static_cast<char *>(ws) + align256(cap * out.norig * kRec * sizeof(float)));
     return OFMK_OK;
 }
 
-// The planar dense search of frames [f0, f0 + cf): clear the chunk's per-phase sums, analyse every even origin (timed as the
-// planar analyze), score every origin under its phase's mean (timed as finalize).
-int psync_scores_chunk(const uint8_t *in, int layout, int f0, int cf, int H, int W, double alpha, long long *scores,
-                       const SyncWorkspace &ws, const Ctx &cx) {
-    PDctSyncGeom g;
-    g.p = make_plane_geom(layout, H, W);
-    g.oh = H / 2 - 3;
-    g.ow = W / 2 - 3;
-    g.rects_x = (g.ow + kPdRectX * kPdStrip - 1) / (kPdRectX * kPdStrip);
+// leaf: analyse every origin of cf frames from `first` (timed as the format's analyze), then score every origin under its
+// phase's mean into `scores` ([cf][64]; timed as finalize)
+void launch_sync_passes(const LeakFmt &f, const uint8_t *first, int cf, double alpha, unsigned long long *scores, const SyncWorkspace &ws,
+                        const Ctx &cx) {
+    if (f.kind == LEAK_YUV420) {
+        PDctSyncGeom g;
+        g.p = make_plane_geom(f);
+        g.oh = f.H / 2 - 3;
+        g.ow = f.W / 2 - 3;
+        g.rects_x = (g.ow + kPdRectX * kPdStrip - 1) / (kPdRectX * kPdStrip);
+        g.norig = ws.norig;
+        g.plane = (size_t)ws.frames * ws.norig;
+        const dim3 grid((unsigned)(g.rects_x * ((g.oh + kPdRectY - 1) / kPdRectY)), (unsigned)cf);
+        {
+            ScopedTiming timing(KIND_PLANAR_ANALYZE, cx);
+            OFMK_TIMED_LAUNCH(timing, dct_sync_analyze_yuv420_kernel, grid, dim3(kThreads), 0, cx.s, first, g, ws.rec, ws.sums);
+        }
+        ScopedTiming timing(KIND_FINALIZE, cx);
+        OFMK_TIMED_LAUNCH(timing, dct_sync_scores_yuv420_kernel, grid, dim3(kThreads), 0, cx.s, g, ws.rec, ws.sums, alpha, scores);
+        return;
+    }
+    DctSyncGeom g;
+    g.H = f.H;
+    g.W = f.W;
+    g.ow = f.W - 7;
+    g.rects_x = (f.W - 7 + kDsRect * kDsStrip - 1) / (kDsRect * kDsStrip);
+    g.frame_stride = f.frame_bytes;
     g.norig = ws.norig;
     g.plane = (size_t)ws.frames * ws.norig;
-    const dim3 grid((unsigned)(g.rects_x * ((g.oh + kPdRectY - 1) / kPdRectY)), (unsigned)cf);
-    HIP_TRY(launch_zero(ws.sums, (size_t)cf * 16 * sizeof(unsigned long long), cx.s));
+    const dim3 grid((unsigned)(g.rects_x * ((f.H - 7 + kDsRect - 1) / kDsRect)), (unsigned)cf);
     {
+        ScopedTiming timing(KIND_ANALYZE, cx);
+        OFMK_TIMED_LAUNCH(timing, dct_sync_analyze_rgb8_kernel, grid, dim3(kThreads), 0, cx.s, first, g, ws.rec, ws.sums);
+    }
+    ScopedTiming timing(KIND_FINALIZE, cx);
+    OFMK_TIMED_LAUNCH(timing, dct_sync_scores_kernel, grid, dim3(kThreads), 0, cx.s, g, ws.rec, ws.sums, alpha, scores);
+}
+
+// leaf: the window's records into ws -- the window's blocks read through the frame's own pitch and stride; ws was carved for
+// them (8 rows x 8 cols pixels)
+int launch_window_analyze(const LeakFmt &f, const uint8_t *first, int cf, int py, int px, int rows, int cols, const Workspace &ws,
+                          const Ctx &cx) {
+    if (f.kind == LEAK_YUV420) {
+        // the grid's x extent is the tile count emit_block files the per-tile sums under, and it is ws.tiles (both are
+        // ceil(nblk / kThreads))
+        const PWinGeom g = make_window_geom(f, rows, cols, cf);
+        const dim3 grid = grid_2d(g.nblk, cf);
+        if ((int)grid.x != ws.tiles) return fail(OFMK_E_ARG, "internal: tile count of the launch and of the workspace differ%s");
         ScopedTiming timing(KIND_PLANAR_ANALYZE, cx);
-        OFMK_TIMED_LAUNCH(timing, dct_sync_analyze_yuv420_kernel, grid, dim3(kThreads), 0, cx.s, in + (size_t)f0 * g.p.frame_stride, g,
-                          ws.rec, ws.sums);
+        OFMK_TIMED_LAUNCH(timing, analyze_window_yuv420_kernel, grid, dim3(kThreads), 0, cx.s, first, g, py, px, ws.plane, ws.rec, ws.ysum);
+        return OFMK_OK;
     }
-    {
-        ScopedTiming timing(KIND_FINALIZE, cx);
-        OFMK_TIMED_LAUNCH(timing, dct_sync_scores_yuv420_kernel, grid, dim3(kThreads), 0, cx.s, g, ws.rec, ws.sums, alpha,
-                          reinterpret_cast<unsigned long long *>(scores) + (size_t)f0 * 64);
-    }
-    HIP_TRY(hipGetLastError());
+    Geom g = make_geom(8 * rows, 8 * cols, ws, cf);
+    g.W = f.W;
+    g.frame_stride = f.frame_bytes;
+    ScopedTiming timing(KIND_ANALYZE, cx);
+    OFMK_TIMED_LAUNCH(timing, (analyze_kernel<SRC_RGB8, false>), xcd_grid(g.nblk, cf), dim3(kThreads), 0, cx.s,
+                      static_cast<const void *>(first + ((size_t)py * f.W + px) * 3), g, ws.rec, ws.ysum, static_cast<int32_t *>(nullptr), 0);
     return OFMK_OK;
 }
 
-// The planar window read-out of frames [f0, f0 + cf): the planar analyze on the window (kind planar analyze), then the soft
-// finalize with canvas positions (kind finalize).  ws was carved for the window's blocks.  The analyze grid's x extent is the
-// tile count emit_block files the per-tile sums under, and it is ws.tiles (both are ceil(nblk / kThreads)).
-int psoft_window_chunk(const uint8_t *in, int layout, int f0, int cf, int H, int W, int py, int px, int rows, int cols, int canvas_cols,
-                       int base, int L, double alpha, long long *soft, const Workspace &ws, const Ctx &cx) {
-    const PWinGeom g = make_window_geom(layout, H, W, rows, cols, cf);
-    const dim3 grid = grid_2d(g.nblk, cf);
-    if ((int)grid.x != ws.tiles) return fail(OFMK_E_ARG, "internal: tile count of the launch and of the workspace differ%s");
-    {
-        ScopedTiming timing(KIND_PLANAR_ANALYZE, cx);
-        OFMK_TIMED_LAUNCH(timing, analyze_window_yuv420_kernel, grid, dim3(kThreads), 0, cx.s, in + (size_t)f0 * g.p.frame_stride, g, py, px,
-                          ws.plane, ws.rec, ws.ysum);
-    }
+// in, scores: checked by the entry point
+int sync_scores(const LeakFmt &f, const uint8_t *in, int n, double alpha, long long *scores, int chunk_frames, void *workspace,
+                size_t workspace_bytes, void *stream, const ofmk_opts *opts) {
+    if (int rc = check_leak(f)) return rc;
+    if (int rc = check_alpha(alpha)) return rc;
+    SyncWorkspace ws;
+    if (int rc = carve_sync(workspace, workspace_bytes, f, chunk_frames, ws)) return rc;
+    const Ctx cx = make_ctx(stream, opts);
+    HIP_TRY(launch_zero(scores, (size_t)n * 64 * sizeof(long long), cx.s));
+    return for_chunks(n, ws.frames, [&](int f0, int cf) {
+        HIP_TRY(launch_zero(ws.sums, (size_t)cf * f.phases * sizeof(unsigned long long), cx.s));
+        launch_sync_passes(f, in + (size_t)f0 * f.frame_bytes, cf, alpha, reinterpret_cast<unsigned long long *>(scores) + (size_t)f0 * 64, ws,
+                           cx);
+        HIP_TRY(hipGetLastError());
+        return (int)OFMK_OK;
+    });
+}
+
+// in, n, H, W, L, soft: checked by the entry point (check_soft_args).  Per chunk: the analyze on the window, then the soft
+// finalize with canvas positions (timed as finalize).
+int soft_window(const LeakFmt &f, const uint8_t *in, int n, int py, int px, int canvas_cols, int base, int L, double alpha, long long *soft,
+                int chunk_frames, void *workspace, size_t workspace_bytes, void *stream, const ofmk_opts *opts) {
+    if (int rc = check_leak(f)) return rc;
+    if (int rc = check_alpha(alpha)) return rc;
+    int rows, cols;
+    if (int rc = check_window(f, py, px, canvas_cols, base, rows, cols)) return rc;
+    Workspace ws;
+    if (int rc = carve(workspace, workspace_bytes, 8 * rows, 8 * cols, chunk_frames, ws)) return rc;
+    const Ctx cx = make_ctx(stream, opts);
+    HIP_TRY(launch_zero(soft, (size_t)n * L * sizeof(long long), cx.s));
     DctWindowArgs a;
     a.rec = ws.rec;
     a.plane = ws.plane;
     a.ysum = ws.ysum;
     a.tiles = ws.tiles;
-    a.nblk = g.nblk;
+    a.nblk = rows * cols;
     a.cols = cols;
     a.canvas_cols = canvas_cols;
     a.base = base;
     a.L = L;
     a.alpha = alpha;
-    a.soft = soft + (size_t)f0 * L;
-    {
-        const int per_wg = kThreads * kFinItems;
-        ScopedTiming timing(KIND_FINALIZE, cx);
-        OFMK_TIMED_LAUNCH(timing, finalize_soft_window_kernel, dim3((unsigned)((a.nblk + per_wg - 1) / per_wg), (unsigned)cf), dim3(kThreads),
-                          0, cx.s, a);
-    }
-    HIP_TRY(hipGetLastError());
-    return OFMK_OK;
+    const int per_wg = kThreads * kFinItems;
+    return for_chunks(n, ws.frames, [&](int f0, int cf) {
+        if (int rc = launch_window_analyze(f, in + (size_t)f0 * f.frame_bytes, cf, py, px, rows, cols, ws, cx)) return rc;
+        a.soft = soft + (size_t)f0 * L;
+        {
+            ScopedTiming timing(KIND_FINALIZE, cx);
+            OFMK_TIMED_LAUNCH(timing, finalize_soft_window_kernel, dim3((unsigned)((a.nblk + per_wg - 1) / per_wg), (unsigned)cf),
+                              dim3(kThreads), 0, cx.s, a);
+        }
+        HIP_TRY(hipGetLastError());
+        return (int)OFMK_OK;
+    });
 }
+
 
 }  // namespace
 
@@ -1582,25 +1657,7 @@ int ofmk_svd_sync_scores_rgb8(const uint8_t *in, int n, int H, int W, const doub
     if (int orc = check_opts(opts)) return orc;
     if (int rc = check_dims(n, H, W)) return rc;
     if (!in || !scores) return fail(OFMK_E_ARG, "null pointer%s");
-    SvdArgs a;
-    if (int rc = check_resync_scales(a, scales, blk, true)) return rc;
-    const Ctx cx = make_ctx(stream, opts);
-    HIP_TRY(launch_zero(scores, (size_t)n * 64 * sizeof(long long), cx.s));
-    SyncGeom g;
-    g.H = H;
-    g.W = W;
-    g.rects_x = (W - 7 + kSyncRect * kSyncStrip - 1) / (kSyncRect * kSyncStrip);
-    g.rects = g.rects_x * ((H - 7 + kSyncRect - 1) / kSyncRect);
-    g.frame_stride = (size_t)H * W * 3;
-    g.scale = a.scales[1];
-    for_chunks(n, kMaxChunk, [&](int f0, int cf) {
-        ScopedTiming timing(KIND_SVD, cx);
-        OFMK_TIMED_LAUNCH(timing, svd_sync_scores_rgb8_kernel, dim3((unsigned)g.rects, (unsigned)cf), dim3(kThreads), 0, cx.s,
-                          in + (size_t)f0 * g.frame_stride, g, reinterpret_cast<unsigned long long *>(scores) + (size_t)f0 * 64);
-        return OFMK_OK;
-    });
-    HIP_TRY(hipGetLastError());
-    return OFMK_OK;
+    return svd_sync_scores(rgb8_leak(H, W), in, n, scales, blk, scores, stream, opts);
 }
 
 // Build extension, not reference semantics (resync_kernels.hiph): the soft read-out of the units at grid phase (py, px) -- unit (i, j)
@@ -1611,32 +1668,7 @@ int ofmk_svd_detect_soft_window_rgb8(const uint8_t *in, int n, int H, int W, int
                                      const double *scales, int blk, long long *soft, void *stream, const ofmk_opts *opts) {
     if (int orc = check_opts(opts)) return orc;
     if (int rc = check_soft_args(in, n, H, W, L, soft)) return rc;
-    if (py < 0 || py > 7 || px < 0 || px > 7) return fail(OFMK_E_ARG, "the phase (py, px) must be in 0..7%s");
-    const int rows = (H - py) / 8, cols = (W - px) / 8;
-    if (rows < 1 || cols < 1) return fail(OFMK_E_ARG, "no full 8x8 unit at this phase%s");
-    if (canvas_cols < cols) return fail(OFMK_E_ARG, "canvas_cols is smaller than the window's units per row%s");
-    if (base < 0) return fail(OFMK_E_ARG, "base must not be negative%s");
-    if ((long long)base + (long long)rows * canvas_cols >= (1LL << 31)) return fail(OFMK_E_ARG, "base + rows * canvas_cols must be < 2^31%s");
-    SvdArgs sa;
-    if (int rc = check_resync_scales(sa, scales, blk, false)) return rc;
-    const Ctx cx = make_ctx(stream, opts);
-    HIP_TRY(launch_zero(soft, (size_t)n * L * sizeof(long long), cx.s));
-    if (!(sa.scales[1] > 0.f)) return OFMK_OK;
-    Geom g = svd_geom(H, W);                 // the frame's W and stride ...
-    g.wb = cols;                             // ... with the window's units
-    g.inv_wb = 1.0f / (float)cols;
-    g.nblk = rows * cols;
-    for_chunks(n, kMaxChunk, [&](int f0, int cf) {
-        ScopedTiming timing(KIND_SVD, cx);
-        Geom gc = g;
-        gc.frames = cf;
-        const WindowArgs w{py, px, canvas_cols, base, L, sa.scales[1], soft + (size_t)f0 * L};
-        OFMK_TIMED_LAUNCH(timing, svd_soft_window_rgb8_kernel, xcd_grid(g.nblk, cf), dim3(kThreads), 0, cx.s,
-                          in + (size_t)f0 * g.frame_stride, gc, w);
-        return OFMK_OK;
-    });
-    HIP_TRY(hipGetLastError());
-    return OFMK_OK;
+    return svd_soft_window(rgb8_leak(H, W), in, n, py, px, canvas_cols, base, L, scales, blk, soft, stream, opts);
 }
 
 // ---- rescaled leaks (warp_kernels.hiph; build extensions, not reference semantics) ---------------------------------------------
@@ -1755,7 +1787,7 @@ int ofmk_svd_detect_soft_warp_rgb8(const uint8_t *in, int n, int h, int w, int H
 // held.  H, W: any values >= 8.
 size_t ofmk_sync_workspace_bytes(int frames_in_flight, int H, int W) {
     if (frames_in_flight < 1 || H < 8 || W < 8 || (long long)H * W >= (1LL << 28)) return 0;
-    return sync_per_frame_bytes(H, W) * (size_t)frames_in_flight + kFixedBytes;
+    return sync_per_frame_bytes(rgb8_leak(H, W)) * (size_t)frames_in_flight + kFixedBytes;
 }
 
 int ofmk_sync_scores_rgb8(const uint8_t *in, int n, int H, int W, double alpha, long long *scores, int chunk_frames, void *workspace,
@@ -1763,12 +1795,7 @@ int ofmk_sync_scores_rgb8(const uint8_t *in, int n, int H, int W, double alpha, 
     if (int orc = check_opts(opts)) return orc;
     if (int rc = check_dims(n, H, W)) return rc;
     if (!in || !scores) return fail(OFMK_E_ARG, "null pointer%s");
-    if (int rc = check_alpha(alpha)) return rc;
-    SyncWorkspace ws;
-    if (int rc = carve_sync(workspace, workspace_bytes, H, W, chunk_frames, ws)) return rc;
-    const Ctx cx = make_ctx(stream, opts);
-    HIP_TRY(launch_zero(scores, (size_t)n * 64 * sizeof(long long), cx.s));
-    return for_chunks(n, ws.frames, [&](int f0, int cf) { return sync_scores_chunk(in, f0, cf, H, W, alpha, scores, ws, cx); });
+    return sync_scores(rgb8_leak(H, W), in, n, alpha, scores, chunk_frames, workspace, workspace_bytes, stream, opts);
 }
 
 // Build extension, not reference semantics (dct_resync_kernels.hiph): the soft read-out of the blocks at grid phase (py, px) -- block
@@ -1780,20 +1807,8 @@ int ofmk_detect_soft_window_rgb8(const uint8_t *in, int n, int H, int W, int py,
                                  const ofmk_opts *opts) {
     if (int orc = check_opts(opts)) return orc;
     if (int rc = check_soft_args(in, n, H, W, L, soft)) return rc;
-    if (int rc = check_alpha(alpha)) return rc;
-    if (py < 0 || py > 7 || px < 0 || px > 7) return fail(OFMK_E_ARG, "the phase (py, px) must be in 0..7%s");
-    const int rows = (H - py) / 8, cols = (W - px) / 8;
-    if (rows < 1 || cols < 1) return fail(OFMK_E_ARG, "no full 8x8 unit at this phase%s");
-    if (canvas_cols < cols) return fail(OFMK_E_ARG, "canvas_cols is smaller than the window's units per row%s");
-    if (base < 0) return fail(OFMK_E_ARG, "base must not be negative%s");
-    if ((long long)base + (long long)rows * canvas_cols >= (1LL << 31)) return fail(OFMK_E_ARG, "base + rows * canvas_cols must be < 2^31%s");
-    Workspace ws;
-    if (int rc = carve(workspace, workspace_bytes, 8 * rows, 8 * cols, chunk_frames, ws)) return rc;
-    const Ctx cx = make_ctx(stream, opts);
-    HIP_TRY(launch_zero(soft, (size_t)n * L * sizeof(long long), cx.s));
-    return for_chunks(n, ws.frames, [&](int f0, int cf) {
-        return soft_window_chunk(in, f0, cf, H, W, py, px, rows, cols, canvas_cols, base, L, alpha, soft, ws, cx);
-    });
+    return soft_window(rgb8_leak(H, W), in, n, py, px, canvas_cols, base, L, alpha, soft, chunk_frames, workspace, workspace_bytes, stream,
+                       opts);
 }
 
 int ofmk_svd_embed_detect_rgb8(const uint8_t *in, uint8_t *out, int n, int H, int W, const uint8_t *wm, int n_wm,
@@ -2160,26 +2175,7 @@ int ofmk_svd_sync_scores_yuv420(const uint8_t *in, int layout, int n, int H, int
     if (int orc = check_opts(opts)) return orc;
     if (int rc = check_dims(n, H, W)) return rc;
     if (!in || !scores) return fail(OFMK_E_ARG, "null pointer%s");
-    if (int rc = check_planar_resync(layout, H, W)) return rc;
-    SvdArgs a;
-    if (int rc = check_resync_scales(a, scales, blk, true)) return rc;
-    const Ctx cx = make_ctx(stream, opts);
-    HIP_TRY(launch_zero(scores, (size_t)n * 64 * sizeof(long long), cx.s));
-    PSyncGeom g;
-    g.p = make_plane_geom(layout, H, W);
-    g.Hc = H / 2;
-    g.Wc = W / 2;
-    g.rects_x = (g.Wc - 3 + kPsRect * kPsStrip - 1) / (kPsRect * kPsStrip);
-    g.scale = a.scales[1];
-    const unsigned rects = (unsigned)(g.rects_x * ((g.Hc - 3 + kPsRect - 1) / kPsRect));
-    for_chunks(n, kMaxChunk, [&](int f0, int cf) {
-        ScopedTiming timing(KIND_SVD, cx);
-        OFMK_TIMED_LAUNCH(timing, svd_sync_scores_yuv420_kernel, dim3(rects, (unsigned)cf), dim3(kThreads), 0, cx.s,
-                          in + (size_t)f0 * g.p.frame_stride, g, reinterpret_cast<unsigned long long *>(scores) + (size_t)f0 * 64);
-        return OFMK_OK;
-    });
-    HIP_TRY(hipGetLastError());
-    return OFMK_OK;
+    return svd_sync_scores(yuv420_leak(layout, H, W), in, n, scales, blk, scores, stream, opts);
 }
 
 // The soft read-out of the units at the even phase (py, px), read through the frame's own pitch, added into position
@@ -2189,30 +2185,13 @@ int ofmk_svd_detect_soft_window_yuv420(const uint8_t *in, int layout, int n, int
                                        const double *scales, int blk, long long *soft, void *stream, const ofmk_opts *opts) {
     if (int orc = check_opts(opts)) return orc;
     if (int rc = check_soft_args(in, n, H, W, L, soft)) return rc;
-    if (int rc = check_planar_resync(layout, H, W)) return rc;
-    int rows, cols;
-    if (int rc = check_planar_window(H, W, py, px, canvas_cols, base, rows, cols)) return rc;
-    SvdArgs sa;
-    if (int rc = check_resync_scales(sa, scales, blk, false)) return rc;
-    const Ctx cx = make_ctx(stream, opts);
-    HIP_TRY(launch_zero(soft, (size_t)n * L * sizeof(long long), cx.s));
-    if (!(sa.scales[1] > 0.f)) return OFMK_OK;
-    for_chunks(n, kMaxChunk, [&](int f0, int cf) {
-        ScopedTiming timing(KIND_SVD, cx);
-        const PWinGeom g = make_window_geom(layout, H, W, rows, cols, cf);
-        const WindowArgs w{py, px, canvas_cols, base, L, sa.scales[1], soft + (size_t)f0 * L};
-        OFMK_TIMED_LAUNCH(timing, svd_soft_window_yuv420_kernel, xcd_grid(g.nblk, cf), dim3(kThreads), 0, cx.s,
-                          in + (size_t)f0 * g.p.frame_stride, g, w);
-        return OFMK_OK;
-    });
-    HIP_TRY(hipGetLastError());
-    return OFMK_OK;
+    return svd_soft_window(yuv420_leak(layout, H, W), in, n, py, px, canvas_cols, base, L, scales, blk, soft, stream, opts);
 }
 
 // The DCT codec's planar search: scratch for `frames_in_flight` frames (12 bytes per EVEN pixel origin and 16 sums per frame).
 size_t ofmk_sync_workspace_bytes_yuv420(int frames_in_flight, int H, int W) {
     if (frames_in_flight < 1 || H < 8 || W < 8 || H % 2 || W % 2 || (long long)H * W >= (1LL << 28)) return 0;
-    return psync_per_frame_bytes(H, W) * (size_t)frames_in_flight + kFixedBytes;
+    return sync_per_frame_bytes(yuv420_leak(OFMK_YUV_I420, H, W)) * (size_t)frames_in_flight + kFixedBytes;      // the same for NV12
 }
 
 // scores[f][8 py + px], even py and px with a full block: the sum of |block metric| of ofmk_detect_soft_yuv420 on the frame's
@@ -2222,13 +2201,7 @@ int ofmk_sync_scores_yuv420(const uint8_t *in, int layout, int n, int H, int W, 
     if (int orc = check_opts(opts)) return orc;
     if (int rc = check_dims(n, H, W)) return rc;
     if (!in || !scores) return fail(OFMK_E_ARG, "null pointer%s");
-    if (int rc = check_planar_resync(layout, H, W)) return rc;
-    if (int rc = check_alpha(alpha)) return rc;
-    SyncWorkspace ws;
-    if (int rc = carve_psync(workspace, workspace_bytes, H, W, chunk_frames, ws)) return rc;
-    const Ctx cx = make_ctx(stream, opts);
-    HIP_TRY(launch_zero(scores, (size_t)n * 64 * sizeof(long long), cx.s));
-    return for_chunks(n, ws.frames, [&](int f0, int cf) { return psync_scores_chunk(in, layout, f0, cf, H, W, alpha, scores, ws, cx); });
+    return sync_scores(yuv420_leak(layout, H, W), in, n, alpha, scores, chunk_frames, workspace, workspace_bytes, stream, opts);
 }
 
 // The soft read-out of the blocks at the even phase (py, px), with canvas positions; masks and frame mean come from the window.
@@ -2238,17 +2211,8 @@ int ofmk_detect_soft_window_yuv420(const uint8_t *in, int layout, int n, int H, 
                                    const ofmk_opts *opts) {
     if (int orc = check_opts(opts)) return orc;
     if (int rc = check_soft_args(in, n, H, W, L, soft)) return rc;
-    if (int rc = check_planar_resync(layout, H, W)) return rc;
-    if (int rc = check_alpha(alpha)) return rc;
-    int rows, cols;
-    if (int rc = check_planar_window(H, W, py, px, canvas_cols, base, rows, cols)) return rc;
-    Workspace ws;
-    if (int rc = carve(workspace, workspace_bytes, 8 * rows, 8 * cols, chunk_frames, ws)) return rc;
-    const Ctx cx = make_ctx(stream, opts);
-    HIP_TRY(launch_zero(soft, (size_t)n * L * sizeof(long long), cx.s));
-    return for_chunks(n, ws.frames, [&](int f0, int cf) {
-        return psoft_window_chunk(in, layout, f0, cf, H, W, py, px, rows, cols, canvas_cols, base, L, alpha, soft, ws, cx);
-    });
+    return soft_window(yuv420_leak(layout, H, W), in, n, py, px, canvas_cols, base, L, alpha, soft, chunk_frames, workspace, workspace_bytes,
+                       stream, opts);
 }
 
 int ofmk_probe_xcc(int32_t *xcc_of_workgroup, int n_workgroups, void *stream, const ofmk_opts *opts) {

@@ -6,6 +6,7 @@ work on torch's current stream; nothing here synchronises.
 """
 from __future__ import annotations
 
+import collections
 import ctypes as C
 import os
 import threading
@@ -81,6 +82,10 @@ def probe_xcc_deal(device=None, workgroups: int = 4096) -> dict:
                    round_robin_fraction=round(fit, 4), workgroups=workgroups)
         _XCC_DEAL[key] = out
         return out
+
+
+# A checked leak of a resync call: lead = the library call's leading arguments (frames, [layout,] n, H, W), suffix = its name's
+_Leak = collections.namedtuple("_Leak", "lead n H W suffix")
 
 
 class DctEngine:
@@ -320,48 +325,79 @@ class DctEngine:
             self._resync_ws[slot] = held
         return held[1]
 
+    def _sync_ws(self, slot, sizing, H, W, frames):
+        nbytes = sizing(min(int(frames), _MAX_CHUNK_FRAMES), H, W)
+        if nbytes == 0:
+            raise _hip.HipError(f"bad frame size {H}x{W}")
+        return self._side_ws(slot, (H, W), nbytes)
+
+    def _window_ws(self, slot, cf, H, W, py, px):
+        """Scratch of a DCT window read-out: workspace() bytes for the window's blocks at phase (py, px)."""
+        if 0 <= py <= 7 and 0 <= px <= 7 and H - py >= 8 and W - px >= 8:
+            h8, w8 = (H - py) // 8 * 8, (W - px) // 8 * 8
+            return self._side_ws(slot, (h8, w8), self.lib.ofmk_workspace_bytes(min(cf, _MAX_CHUNK_FRAMES), h8, w8))
+        return self._side_ws(slot, (8, 8), self.lib.ofmk_workspace_bytes(1, 8, 8))       # the library refuses the phase
+
+    # The resync calls come as an RGB and a 4:2:0 method with one private body: the leak descriptor carries what differs, the
+    # library call's leading arguments and its name's suffix.
+    def _rgb_leak(self, frames):
+        n, H, W = self._check_frames(frames, self.torch.uint8)
+        return _Leak((frames.data_ptr(), n, H, W), n, H, W, "rgb8")
+
+    def _planar_leak(self, planes, H, W, layout):
+        n = self._check_planar_even(planes, H, W)
+        return _Leak((planes.data_ptr(), self._layout(layout), n, H, W), n, H, W, "yuv420")
+
+    def _resync_call(self, name, leak, *args):
+        _hip.check(getattr(self.lib, f"ofmk_{name}_{leak.suffix}")(*leak.lead, *args, _hip.current_stream(), self._o()))
+
+    def _sync_scores(self, leak, share, workspace, alpha, scores):
+        """share: the part of the frame budget a chunk takes, so that its records stay at the frames' size."""
+        scores = self._soft(scores, leak.n, 64)
+        cf = balanced_chunk(leak.n, max(1, (self.chunk_frames or default_chunk_frames(leak.H, leak.W)) // share))
+        ws = workspace(leak.H, leak.W, cf)
+        self._resync_call("sync_scores", leak, float(alpha), scores.data_ptr(), cf, ws.data_ptr(), ws.numel())
+        return scores
+
+    def _detect_soft_window(self, leak, slot, L, phase, canvas_cols, base, alpha, soft):
+        soft = self._soft(soft, leak.n, L)
+        py, px = (int(v) for v in phase)
+        cf = self._chunk(leak.n, leak.H, leak.W)
+        ws = self._window_ws(slot, cf, leak.H, leak.W, py, px)
+        self._resync_call("detect_soft_window", leak, py, px, int(canvas_cols), int(base), int(L), float(alpha), soft.data_ptr(), cf,
+                          ws.data_ptr(), ws.numel())
+        return soft
+
+    def _svd_sync_scores(self, leak, scale, scales, blk, scores):
+        scores = self._soft(scores, leak.n, 64)
+        self._resync_call("svd_sync_scores", leak, _hip.scales3(scale, scales), int(blk), scores.data_ptr())
+        return scores
+
+    def _svd_detect_soft_window(self, leak, L, phase, canvas_cols, base, scale, scales, blk, soft):
+        soft = self._soft(soft, leak.n, L)
+        py, px = phase
+        self._resync_call("svd_detect_soft_window", leak, int(py), int(px), int(canvas_cols), int(base), int(L), _hip.scales3(scale, scales),
+                          int(blk), soft.data_ptr())
+        return soft
+
     def sync_workspace(self, H: int, W: int, frames: int):
         """Scratch of sync_scores for `frames` frames in flight (ofmk_sync_workspace_bytes: one record per pixel origin).  A cache
         of its own: the ordinary workspace() buffer is neither replaced nor freed."""
-        nbytes = self.lib.ofmk_sync_workspace_bytes(min(int(frames), _MAX_CHUNK_FRAMES), H, W)
-        if nbytes == 0:
-            raise _hip.HipError(f"bad frame size {H}x{W}")
-        return self._side_ws("sync", (H, W), nbytes)
+        return self._sync_ws("sync", self.lib.ofmk_sync_workspace_bytes, H, W, frames)
 
     def sync_scores(self, frames, alpha=20, scores=None):
         """The dense phase search: int64 [n, 64], entry 8 * py + px = the sum of |block metric| over the full 8x8 windows of the
         frame at grid phase (py, px), i.e. ``detect_soft(crop, blocks, alpha).abs().sum(1)`` of the contiguous crop that holds the
         phase's blocks -- masks and frame mean taken from that crop -- integer for integer.  H and W are any values >= 8.
         offmark.resync.best_phase reads it."""
-        t = self.torch
-        n, H, W = self._check_frames(frames, t.uint8)
-        scores = self._soft(scores, n, 64)
         # 12 bytes per pixel origin against 3 per pixel: a quarter of the frame budget keeps the records at the frames' size
-        cf = balanced_chunk(n, max(1, (self.chunk_frames or default_chunk_frames(H, W)) // 4))
-        ws = self.sync_workspace(H, W, cf)
-        _hip.check(self.lib.ofmk_sync_scores_rgb8(frames.data_ptr(), n, H, W, float(alpha), scores.data_ptr(), cf, ws.data_ptr(),
-                                                  ws.numel(), _hip.current_stream(), self._o()))
-        return scores
+        return self._sync_scores(self._rgb_leak(frames), 4, self.sync_workspace, alpha, scores)
 
     def detect_soft_window(self, frames, L, phase, canvas_cols, base=0, alpha=20, soft=None):
         """detect_soft of the blocks at grid ``phase`` = (py, px): block (i, j) is the 8x8 block at pixel (py + 8i, px + 8j) and
         adds into position (base + i * canvas_cols + j) % L, the position it has in a frame ``canvas_cols`` blocks wide.  Masks
         and frame mean come from the window.  int64 [n, L]."""
-        t = self.torch
-        n, H, W = self._check_frames(frames, t.uint8)
-        soft = self._soft(soft, n, L)
-        py, px = (int(v) for v in phase)
-        cf = self._chunk(n, H, W)
-        if 0 <= py <= 7 and 0 <= px <= 7 and H - py >= 8 and W - px >= 8:
-            h8, w8 = (H - py) // 8 * 8, (W - px) // 8 * 8
-            nbytes = self.lib.ofmk_workspace_bytes(min(cf, _MAX_CHUNK_FRAMES), h8, w8)
-            ws = self._side_ws("window", (h8, w8), nbytes)
-        else:
-            ws = self._side_ws("window", (8, 8), self.lib.ofmk_workspace_bytes(1, 8, 8))       # the library refuses the phase
-        _hip.check(self.lib.ofmk_detect_soft_window_rgb8(frames.data_ptr(), n, H, W, py, px, int(canvas_cols), int(base), int(L),
-                                                         float(alpha), soft.data_ptr(), cf, ws.data_ptr(), ws.numel(),
-                                                         _hip.current_stream(), self._o()))
-        return soft
+        return self._detect_soft_window(self._rgb_leak(frames), "window", L, phase, canvas_cols, base, alpha, soft)
 
     def embed_detect(self, frames, wm, L, alpha=20, wm_row=None, out=None, want_bits=False, counts=None):
         """Mark, then read back the marked frames chunk by chunk (mark + verify)."""
@@ -577,24 +613,12 @@ class DctEngine:
     def svd_sync_scores(self, frames, scale=15, scales=None, blk=4, scores=None):
         """The dense phase search: int64 [n, 64], entry 8 * py + px = the sum of |unit metric| (svd_detect_soft's, blk 4) over the
         full 8x8 windows of the frame at grid phase (py, px).  H and W are any values >= 8.  offmark.resync.best_phase reads it."""
-        t = self.torch
-        n, H, W = self._check_frames(frames, t.uint8)
-        scores = self._soft(scores, n, 64)
-        _hip.check(self.lib.ofmk_svd_sync_scores_rgb8(frames.data_ptr(), n, H, W, _hip.scales3(scale, scales), int(blk), scores.data_ptr(),
-                                                      _hip.current_stream(), self._o()))
-        return scores
+        return self._svd_sync_scores(self._rgb_leak(frames), scale, scales, blk, scores)
 
     def svd_detect_soft_window(self, frames, L, phase, canvas_cols, base=0, scale=15, scales=None, blk=4, soft=None):
         """svd_detect_soft of the units at grid ``phase`` = (py, px): unit (i, j) is the 8x8 block at pixel (py + 8i, px + 8j) and
         adds into position (base + i * canvas_cols + j) % L, the position it has in a frame ``canvas_cols`` units wide.  int64 [n, L]."""
-        t = self.torch
-        n, H, W = self._check_frames(frames, t.uint8)
-        soft = self._soft(soft, n, L)
-        py, px = phase
-        _hip.check(self.lib.ofmk_svd_detect_soft_window_rgb8(frames.data_ptr(), n, H, W, int(py), int(px), int(canvas_cols), int(base), int(L),
-                                                             _hip.scales3(scale, scales), int(blk), soft.data_ptr(), _hip.current_stream(),
-                                                             self._o()))
-        return soft
+        return self._svd_detect_soft_window(self._rgb_leak(frames), L, phase, canvas_cols, base, scale, scales, blk, soft)
 
     # -- rescaled leaks: fixed-point warp onto the marked frame's canvas (build extension; blk 4, channel 1; offmark.resync) -----
     @staticmethod
@@ -830,65 +854,33 @@ class DctEngine:
         svd_detect_soft_yuv420 (blk 4) over the units of the frame's sub-planes for the pixel window [py:py + 8r, px:px + 8c],
         r = (H - py) // 8, c = (W - px) // 8 -- the even entries of svd_sync_scores(yuv420_to_rgb(planes)), integer for integer.
         Odd phases and phases without a unit are 0.  offmark.resync.best_phase(..., even_only=True) reads it."""
-        n = self._check_planar_even(planes, H, W)
-        scores = self._soft(scores, n, 64)
-        _hip.check(self.lib.ofmk_svd_sync_scores_yuv420(planes.data_ptr(), self._layout(layout), n, H, W, _hip.scales3(scale, scales),
-                                                        int(blk), scores.data_ptr(), _hip.current_stream(), self._o()))
-        return scores
+        return self._svd_sync_scores(self._planar_leak(planes, H, W, layout), scale, scales, blk, scores)
 
     def svd_detect_soft_window_yuv420(self, planes, H, W, L, phase, canvas_cols, base=0, scale=15, scales=None, blk=4, layout="i420",
                                       soft=None):
         """svd_detect_soft_yuv420 of the units at the even grid ``phase`` = (py, px): unit (i, j) is the 8x8 block at pixel
         (py + 8i, px + 8j), read through the frame's own pitch, and adds into position (base + i * canvas_cols + j) % L.
         int64 [n, L]."""
-        n = self._check_planar_even(planes, H, W)
-        soft = self._soft(soft, n, L)
-        py, px = phase
-        _hip.check(self.lib.ofmk_svd_detect_soft_window_yuv420(planes.data_ptr(), self._layout(layout), n, H, W, int(py), int(px),
-                                                               int(canvas_cols), int(base), int(L), _hip.scales3(scale, scales), int(blk),
-                                                               soft.data_ptr(), _hip.current_stream(), self._o()))
-        return soft
+        return self._svd_detect_soft_window(self._planar_leak(planes, H, W, layout), L, phase, canvas_cols, base, scale, scales, blk, soft)
 
     def sync_workspace_yuv420(self, H: int, W: int, frames: int):
         """Scratch of sync_scores_yuv420 for `frames` frames in flight (ofmk_sync_workspace_bytes_yuv420: one record per even
         pixel origin).  A cache of its own, as sync_workspace()."""
-        nbytes = self.lib.ofmk_sync_workspace_bytes_yuv420(min(int(frames), _MAX_CHUNK_FRAMES), H, W)
-        if nbytes == 0:
-            raise _hip.HipError(f"bad frame size {H}x{W}")
-        return self._side_ws("sync420", (H, W), nbytes)
+        return self._sync_ws("sync420", self.lib.ofmk_sync_workspace_bytes_yuv420, H, W, frames)
 
     def sync_scores_yuv420(self, planes, H, W, alpha=20, layout="i420", scores=None):
         """The DCT codec's dense phase search on planes: int64 [n, 64].  For even py and px, entry 8 * py + px =
         ``detect_soft_yuv420(sub, blocks, alpha).abs().sum(1)`` of the frame's sub-planes for the pixel window [py:py + 8r,
         px:px + 8c] -- masks and frame mean taken from that sub-frame -- integer for integer, which is also that entry of
         sync_scores(yuv420_to_rgb(planes)).  Odd phases and phases without a block are 0."""
-        n = self._check_planar_even(planes, H, W)
-        scores = self._soft(scores, n, 64)
         # 3 bytes of records per pixel against 1.5 of planes: half the frame budget keeps the records at the frames' size
-        cf = balanced_chunk(n, max(1, (self.chunk_frames or default_chunk_frames(H, W)) // 2))
-        ws = self.sync_workspace_yuv420(H, W, cf)
-        _hip.check(self.lib.ofmk_sync_scores_yuv420(planes.data_ptr(), self._layout(layout), n, H, W, float(alpha), scores.data_ptr(), cf,
-                                                    ws.data_ptr(), ws.numel(), _hip.current_stream(), self._o()))
-        return scores
+        return self._sync_scores(self._planar_leak(planes, H, W, layout), 2, self.sync_workspace_yuv420, alpha, scores)
 
     def detect_soft_window_yuv420(self, planes, H, W, L, phase, canvas_cols, base=0, alpha=20, layout="i420", soft=None):
         """detect_soft_yuv420 of the blocks at the even grid ``phase`` = (py, px): block (i, j) is the 8x8 block at pixel
         (py + 8i, px + 8j), read through the frame's own pitch, and adds into position (base + i * canvas_cols + j) % L.  Masks
         and frame mean come from the window.  int64 [n, L]."""
-        n = self._check_planar_even(planes, H, W)
-        soft = self._soft(soft, n, L)
-        py, px = (int(v) for v in phase)
-        cf = self._chunk(n, H, W)
-        if 0 <= py <= 7 and 0 <= px <= 7 and H - py >= 8 and W - px >= 8:
-            h8, w8 = (H - py) // 8 * 8, (W - px) // 8 * 8
-            nbytes = self.lib.ofmk_workspace_bytes(min(cf, _MAX_CHUNK_FRAMES), h8, w8)
-            ws = self._side_ws("window420", (h8, w8), nbytes)
-        else:
-            ws = self._side_ws("window420", (8, 8), self.lib.ofmk_workspace_bytes(1, 8, 8))    # the library refuses the phase
-        _hip.check(self.lib.ofmk_detect_soft_window_yuv420(planes.data_ptr(), self._layout(layout), n, H, W, py, px, int(canvas_cols),
-                                                           int(base), int(L), float(alpha), soft.data_ptr(), cf, ws.data_ptr(), ws.numel(),
-                                                           _hip.current_stream(), self._o()))
-        return soft
+        return self._detect_soft_window(self._planar_leak(planes, H, W, layout), "window420", L, phase, canvas_cols, base, alpha, soft)
 
     def svd_embed_detect_yuv420(self, planes, H, W, wm, L, scale=15, wm_row=None, out=None, want_bits=False, scales=None, blk=4,
                                 counts=None, partial=False, layout="i420"):

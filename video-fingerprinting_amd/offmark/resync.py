@@ -54,6 +54,18 @@ def units_per_phase(H: int, W: int) -> np.ndarray:
     return (r[:, None] * c[None, :]).reshape(64)
 
 
+def _rank(s: np.ndarray, units: np.ndarray, have: np.ndarray) -> tuple:
+    """The ranking behind best_phase and best_geometry.  s: int64 [n, K] scores (rows are added); units: int64 [K] units behind
+    each entry; have: bool [K], the entries that take part (at least one) -> (normalised float64 [K], 0 where not ``have``; the
+    best entry's index, the first on a tie; contrast = best / second best, inf when there is no second or it scores 0)."""
+    norm = np.zeros(units.size, np.float64)
+    norm[have] = s.sum(axis=0)[have] / (float(ONE) * units[have] * s.shape[0])
+    order = np.argsort(-np.where(have, norm, -1.0), kind="stable")
+    top = int(order[0])
+    second = float(norm[order[1]]) if have.sum() > 1 else 0.0
+    return norm, top, float(norm[top] / second) if second > 0 else float("inf")
+
+
 def best_phase(scores, H: int, W: int, even_only: bool = False) -> dict:
     """scores: [64] or [n, 64] sums of |soft metric| per phase (rows are added) of H x W frames ->
     dict(phase=(py, px), normalised=float64 [64], contrast=top / second).  normalised = score / (2^14 * units * frames): about 1
@@ -69,12 +81,7 @@ def best_phase(scores, H: int, W: int, even_only: bool = False) -> dict:
         have &= (even[:, None] & even[None, :]).reshape(64)
     if not have.any():
         raise ValueError(f"a {H}x{W} frame holds no 8x8 unit")
-    norm = np.zeros(64, np.float64)
-    norm[have] = s.sum(axis=0)[have] / (float(ONE) * units[have] * s.shape[0])
-    order = np.argsort(-np.where(have, norm, -1.0), kind="stable")
-    top = int(order[0])
-    second = float(norm[order[1]]) if have.sum() > 1 else 0.0
-    contrast = float(norm[top] / second) if second > 0 else float("inf")
+    norm, top, contrast = _rank(s, units, have)
     return dict(phase=(top // 8, top % 8), normalised=norm, contrast=contrast)
 
 
@@ -131,6 +138,22 @@ def _host(x) -> np.ndarray:
     return np.asarray(x.cpu() if hasattr(x, "cpu") else x)
 
 
+def _align_by_segment(soft, segment_of_frame, candidates, key, bases=None) -> dict:
+    """The tail of the read_*_leak recipes.  soft: [n, L] soft sums per frame; segment_of_frame: [n] labels -> align_segments of
+    the sums per segment (candidates in the order of the sorted distinct labels, or a dict keyed by label), with ``segments``
+    (the sorted labels) and ``soft_by_segment`` added."""
+    soft = _host(soft).astype(np.int64)
+    seg = np.asarray(segment_of_frame).reshape(-1)
+    if seg.size != soft.shape[0]:
+        raise ValueError("segment_of_frame needs one entry per frame")
+    labels = sorted(set(seg.tolist()))
+    by_segment = np.stack([soft[seg == s].sum(axis=0) for s in labels])
+    cands = [candidates[s] for s in labels] if isinstance(candidates, dict) else list(candidates)
+    out = align_segments(by_segment, cands, key, bases)
+    out.update(segments=labels, soft_by_segment=by_segment)
+    return out
+
+
 def read_cropped_leak(decoder, frames, segment_of_frame, canvas_width: int, candidates, key=0, L: int = 8, search_frames: int = 8) -> dict:
     """A cropped leak's copy per segment.  decoder: a DwtDctSvdDecoder (blk 4) or a DctDecoder (anything with their
     sync_scores_u8 / decode_soft_window_u8); frames: CUDA uint8 [n, H, W, 3], the leak as it is
@@ -142,17 +165,11 @@ def read_cropped_leak(decoder, frames, segment_of_frame, canvas_width: int, cand
     With a DctDecoder the masks and the frame mean come from the leak as received, so the right phase reads near, not at, +-2^14
     per block and ``contrast`` is lower than DwtDctSvd's: 1.18 on the marked test recipe against 1.005 on its unmarked sources
     (module docstring)."""
-    n, H, W = int(frames.shape[0]), int(frames.shape[1]), int(frames.shape[2])
-    seg = np.asarray(segment_of_frame).reshape(-1)
-    if seg.size != n:
-        raise ValueError("segment_of_frame needs one entry per frame")
+    H, W = int(frames.shape[1]), int(frames.shape[2])
     found = best_phase(_host(decoder.sync_scores_u8(frames[:max(1, int(search_frames))])), H, W)
-    soft = _host(decoder.decode_soft_window_u8(frames, L, found["phase"], int(canvas_width) // 8, base=0)).astype(np.int64)
-    labels = sorted(set(seg.tolist()))
-    by_segment = np.stack([soft[seg == s].sum(axis=0) for s in labels])
-    cands = [candidates[s] for s in labels] if isinstance(candidates, dict) else list(candidates)
-    out = align_segments(by_segment, cands, key)
-    out.update(phase=found["phase"], contrast=found["contrast"], normalised=found["normalised"], segments=labels, soft_by_segment=by_segment)
+    soft = decoder.decode_soft_window_u8(frames, L, found["phase"], int(canvas_width) // 8, base=0)
+    out = _align_by_segment(soft, segment_of_frame, candidates, key)
+    out.update(phase=found["phase"], contrast=found["contrast"], normalised=found["normalised"])
     return out
 
 
@@ -163,18 +180,11 @@ def read_cropped_leak_yuv420(decoder, planes, height: int, width: int, segment_o
     decode_soft_window_planes_yuv420); planes: CUDA uint8 [n, 1.5 * height * width] in ``layout`` ("i420" / "nv12"), height and
     width even and >= 8; the other arguments and the returned dict as read_cropped_leak.  The phase search ranks the 16 even
     phases only (best_phase(..., even_only=True)); nothing is converted to RGB."""
-    n, H, W = int(planes.shape[0]), int(height), int(width)
-    seg = np.asarray(segment_of_frame).reshape(-1)
-    if seg.size != n:
-        raise ValueError("segment_of_frame needs one entry per frame")
+    H, W = int(height), int(width)
     found = best_phase(_host(decoder.sync_scores_planes_yuv420(planes[:max(1, int(search_frames))], H, W, layout=layout)), H, W, even_only=True)
-    soft = _host(decoder.decode_soft_window_planes_yuv420(planes, H, W, L, found["phase"], int(canvas_width) // 8, base=0,
-                                                          layout=layout)).astype(np.int64)
-    labels = sorted(set(seg.tolist()))
-    by_segment = np.stack([soft[seg == s].sum(axis=0) for s in labels])
-    cands = [candidates[s] for s in labels] if isinstance(candidates, dict) else list(candidates)
-    out = align_segments(by_segment, cands, key)
-    out.update(phase=found["phase"], contrast=found["contrast"], normalised=found["normalised"], segments=labels, soft_by_segment=by_segment)
+    soft = decoder.decode_soft_window_planes_yuv420(planes, H, W, L, found["phase"], int(canvas_width) // 8, base=0, layout=layout)
+    out = _align_by_segment(soft, segment_of_frame, candidates, key)
+    out.update(phase=found["phase"], contrast=found["contrast"], normalised=found["normalised"])
     return out
 
 
@@ -254,12 +264,7 @@ def best_geometry(scores, cands, leak_hw, canvas_hw) -> dict:
     have = units > 0
     if not have.any():
         raise ValueError("no candidate geometry has a counting unit")
-    norm = np.zeros(K, np.float64)
-    norm[have] = s.sum(axis=0)[have] / (float(ONE) * units[have] * s.shape[0])
-    order = np.argsort(-np.where(have, norm, -1.0), kind="stable")
-    top = int(order[0])
-    second = float(norm[order[1]]) if have.sum() > 1 else 0.0
-    contrast = float(norm[top] / second) if second > 0 else float("inf")
+    norm, top, contrast = _rank(s, units, have)
     return dict(index=top, geometry=tuple(int(v) for v in cands[top]), normalised=norm, contrast=contrast)
 
 
@@ -273,12 +278,8 @@ def read_rescaled_leak(decoder, frames, segment_of_frame, canvas_hw, candidates,
     that correlates best with the position rotation fixed at 0 (canvas coordinates leave none).  -> dict(geometry, index,
     contrast, normalised (None, None without a search), segments, soft_by_segment, base (0), picks, score, runner_up_score
     (None), ambiguous).  No verdict on ``contrast``."""
-    n = int(frames.shape[0])
     leak_hw = (int(frames.shape[1]), int(frames.shape[2]))
     canvas_hw = (int(canvas_hw[0]), int(canvas_hw[1]))
-    seg = np.asarray(segment_of_frame).reshape(-1)
-    if seg.size != n:
-        raise ValueError("segment_of_frame needs one entry per frame")
     geoms = np.asarray(_host(geometries), dtype=np.int64).reshape(-1, 4)
     if geoms.shape[0] < 1:
         raise ValueError("geometries must hold at least one (ay, by, ax, bx)")
@@ -288,11 +289,7 @@ def read_rescaled_leak(decoder, frames, segment_of_frame, canvas_hw, candidates,
         found = best_geometry(_host(decoder.warp_scores_u8(frames[:max(1, int(search_frames))], canvas_hw, geoms)), geoms, leak_hw, canvas_hw)
     else:
         found = dict(index=0, geometry=tuple(int(v) for v in geoms[0]), normalised=None, contrast=None)
-    soft = _host(decoder.decode_soft_warp_u8(frames, canvas_hw, found["geometry"], L)).astype(np.int64)
-    labels = sorted(set(seg.tolist()))
-    by_segment = np.stack([soft[seg == s].sum(axis=0) for s in labels])
-    cands = [candidates[s] for s in labels] if isinstance(candidates, dict) else list(candidates)
-    out = align_segments(by_segment, cands, key, bases=(0,))
-    out.update(geometry=found["geometry"], index=found["index"], contrast=found["contrast"], normalised=found["normalised"], segments=labels,
-               soft_by_segment=by_segment)
+    soft = decoder.decode_soft_warp_u8(frames, canvas_hw, found["geometry"], L)
+    out = _align_by_segment(soft, segment_of_frame, candidates, key, bases=(0,))
+    out.update(geometry=found["geometry"], index=found["index"], contrast=found["contrast"], normalised=found["normalised"])
     return out
