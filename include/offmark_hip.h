@@ -583,6 +583,47 @@ int ofmk_svd_warp_scores_rgb8(const uint8_t *in, int n, int h, int w, int H, int
 int ofmk_svd_detect_soft_warp_rgb8(const uint8_t *in, int n, int h, int w, int H, int W, const ofmk_warp *geom, int L,
                                    const double *scales, int blk, long long *soft, void *stream, const ofmk_opts *opts);
 
+/* ---- reading ROTATED leaks: the same warp under a 2x3 affine map (BUILD EXTENSION) ---------------------------------------------
+ * The rescaled-leak calls above with a full affine map: rotation, shear, anisotropic scale, flips and 90 degree turns.  Interleaved
+ * u8 RGB, blk 4, YUV channel 1.
+ *
+ *   ofmk_affine {ayy, ayx, by, axy, axx, bx}, Q16.  Canvas pixel (y, x) reads the leak (h x w) at
+ *       pos_y = ayy*y + ayx*x + by      pos_x = axy*y + axx*x + bx      (int64)
+ *   and everything else is ofmk_warp's rule, word for word: y0 = pos_y >> 16, fy = (pos_y >> 8) & 255, columns alike; INSIDE iff
+ *   0 <= y0 <= h-1 and 0 <= x0 <= w-1; second taps min(y0+1, h-1), min(x0+1, w-1); per channel
+ *       v = ((256-fy)*((256-fx)*p00 + fx*p01) + fy*((256-fx)*p10 + fx*p11) + 32768) >> 16
+ *   and 0 outside.  ayx = axy = 0 is ofmk_warp {ayy, by, axx, bx} byte for byte.  Negative coefficients are allowed:
+ *   {65536, 0, 0, 0, -65536, (w-1) << 16} returns the frame mirrored left to right.
+ *   Required, else OFMK_E_ARG: the four coefficients in [-2^20, 2^20], |by|, |bx| <= 2^48 (pos then stays far inside int64) and
+ *   |ayy*axx - ayx*axy| >= 2^24 (the square of ofmk_warp's smallest scale).
+ *   offmark.resync.affine_of_rotation gives the map of a leak rotated and scaled about its centre.
+ *   Canvas unit (i, j), i < H/8, j < W/8, COUNTS iff all 64 of its pixels are inside.  Positions are affine and the inside set is an
+ *   intersection of half-planes, so that is: iff its 4 corner pixels (8i, 8j), (8i, 8j+7), (8i+7, 8j), (8i+7, 8j+7) are inside.  The
+ *   counting units are convex, not a rectangle.
+ *
+ * ofmk_affine_units: host only, no GPU call.  out = {i0, i1, j0, j1, count}: the bounding rectangle [i0, i1) x [j0, j1) of the
+ *   counting units and how many count; all 0 when none does.  Argument rules as ofmk_warp_units.
+ * ofmk_warp_affine_rgb8: as ofmk_warp_rgb8 -- out is the canvas rectangle with top-left canvas pixel (oy, ox), every byte is
+ *   written, geom is HOST memory, same argument rules.
+ * ofmk_svd_affine_scores_rgb8: as ofmk_svd_warp_scores_rgb8 with cands DEVICE memory, ofmk_affine [K] (an int64 [K][6] array).
+ *   scores is cleared by the call; a candidate out of range scores 0 (the list is not read on the host), and so does one without
+ *   a counting unit.  Candidates in gridDim.y and frames in gridDim.z, chunked at 65535 and below 2^30 workgroups per launch.
+ *   One thread per canvas unit and candidate, a workgroup per tile of 16 x 16 units; a pixel's two taps of one leak row are
+ *   fetched together (6 adjacent bytes).  No warped frame is written.
+ * ofmk_svd_detect_soft_affine_rgb8: as ofmk_svd_detect_soft_warp_rgb8 -- counting unit (i, j) adds m into position
+ *   (i * (W/8) + j) mod L; soft is cleared by the call; scales[1] <= 0 or no counting unit: all zeros.  Equal, integer for integer,
+ *   to ofmk_warp_affine_rgb8 of the canvas followed by the soft read-out of the counting units at their canvas positions.
+ * The three device calls allocate nothing, synchronise nothing and are graph capturable; all three are timed as kind 4 (svd);
+ * OFMK_F_PARTIAL_COUNTS and the tile-order flags are ignored.  Argument checks: those of the ofmk_warp counterparts. */
+typedef struct ofmk_affine { int64_t ayy, ayx, by, axy, axx, bx; } ofmk_affine;
+int ofmk_affine_units(int h, int w, int H, int W, const ofmk_affine *geom, int out[5]);
+int ofmk_warp_affine_rgb8(const uint8_t *in, int n, int h, int w, uint8_t *out, int Hout, int Wout, int oy, int ox,
+                          const ofmk_affine *geom, void *stream, const ofmk_opts *opts);
+int ofmk_svd_affine_scores_rgb8(const uint8_t *in, int n, int h, int w, int H, int W, const ofmk_affine *cands, int K,
+                                const double *scales, int blk, long long *scores, void *stream, const ofmk_opts *opts);
+int ofmk_svd_detect_soft_affine_rgb8(const uint8_t *in, int n, int h, int w, int H, int W, const ofmk_affine *geom, int L,
+                                     const double *scales, int blk, long long *soft, void *stream, const ofmk_opts *opts);
+
 /* ---- DeShuffler.degenerate's epilogue for a batch, on the device ---------------------------
  * src/offmark/degenerator/de_shuffler.py:17-22: mean of bits[i::L] (from `counts`), undo the key
  * permutation (`perm` = DeShuffler.payload_idx, device int32 [L]), threshold strictly above the

@@ -51,6 +51,7 @@
 #include "dct_resync_kernels.hiph"
 #include "planar_resync_kernels.hiph"
 #include "warp_kernels.hiph"
+#include "affine_kernels.hiph"
 
 namespace {
 
@@ -872,6 +873,52 @@ void warp_rect(const WarpMap &m, int h, int w, int H, int W, int out[4]) {
     warp_axis_units(m.ax, m.bx, w, W / 8, j0, j1);
     const bool any = i0 < i1 && j0 < j1;
     out[0] = any ? i0 : 0; out[1] = any ? i1 : 0; out[2] = any ? j0 : 0; out[3] = any ? j1 : 0;
+}
+
+// ---- rotated leaks (affine_kernels.hiph) ---------------------------------------------------------------------------------------
+static_assert(sizeof(AffineMap) == sizeof(ofmk_affine) && sizeof(ofmk_affine) == 48, "ofmk_affine is six int64");
+
+int check_affine_map(const ofmk_affine *geom, AffineMap &m) {
+    m.ayy = geom->ayy; m.ayx = geom->ayx; m.by = geom->by; m.axy = geom->axy; m.axx = geom->axx; m.bx = geom->bx;
+    if (!affine_map_ok(m))
+        return fail(OFMK_E_ARG, "ofmk_affine: coefficients must be in [-2^20, 2^20], |by|, |bx| <= 2^48 and |ayy*axx - ayx*axy| >= 2^24%s");
+    return OFMK_OK;
+}
+
+// The integers j with a * j + c >= 0, cut out of [lo, hi].
+void affine_bound(long long a, long long c, long long &lo, long long &hi) {
+    if (a == 0) {
+        if (c < 0) hi = -1;                                     // lo >= 0 throughout: empty
+        return;
+    }
+    const long long d = a > 0 ? a : -a, n = a > 0 ? -c + a - 1 : c;      // a > 0: j >= ceil(-c / a); a < 0: j <= floor(c / -a)
+    long long q = n / d;
+    if (n % d < 0) --q;
+    if (a > 0) lo = q > lo ? q : lo;
+    else hi = q < hi ? q : hi;
+}
+
+// out = {i0, i1, j0, j1, count}: the bounding rectangle of the counting units and how many count; all 0 when none does.  Each of a
+// unit's 16 conditions (4 corner pixels x 4 edges of the leak) is linear in j, so a row of units counts on an interval of j.
+void affine_rect(const AffineMap &m, int h, int w, int H, int W, int out[5]) {
+    const int rows = H / 8, cols = W / 8;
+    int i0 = rows, i1 = 0, j0 = cols, j1 = 0, count = 0;
+    for (int i = 0; i < rows; ++i) {
+        long long lo = 0, hi = cols - 1;
+        for (int corner = 0; corner < 4; ++corner) {
+            const int y = 8 * i + (corner & 2 ? 7 : 0), dx = corner & 1 ? 7 : 0;
+            const long long cy = affine_pos_y(m, y, dx), cx = affine_pos_x(m, y, dx);      // pixel (y, 8 j + dx): cy + 8 ayx j, cx + 8 axx j
+            affine_bound(8 * m.ayx, cy, lo, hi);
+            affine_bound(-8 * m.ayx, ((long long)h << 16) - 1 - cy, lo, hi);
+            affine_bound(8 * m.axx, cx, lo, hi);
+            affine_bound(-8 * m.axx, ((long long)w << 16) - 1 - cx, lo, hi);
+        }
+        if (lo > hi) continue;
+        i0 = i < i0 ? i : i0; i1 = i + 1;
+        j0 = (int)lo < j0 ? (int)lo : j0; j1 = (int)hi + 1 > j1 ? (int)hi + 1 : j1;
+        count += (int)(hi - lo + 1);
+    }
+    out[0] = count ? i0 : 0; out[1] = i1; out[2] = count ? j0 : 0; out[3] = j1; out[4] = count;
 }
 
 // ---- C marked copies of the same frames (copies_kernels.hiph) -------------------------------------------------------
@@ -1776,6 +1823,118 @@ int ofmk_svd_detect_soft_warp_rgb8(const uint8_t *in, int n, int h, int w, int H
         ac.frames = cf;
         ac.soft = soft + (size_t)f0 * L;
         OFMK_TIMED_LAUNCH(timing, svd_soft_warp_rgb8_kernel, xcd_grid(a.nunits, cf), dim3(kThreads), 0, cx.s, in + (size_t)f0 * a.frame_stride, ac);
+        return OFMK_OK;
+    });
+    HIP_TRY(hipGetLastError());
+    return OFMK_OK;
+}
+
+// ---- rotated leaks (affine_kernels.hiph; build extensions, not reference semantics) --------------------------------------------
+// Host only: out = {i0, i1, j0, j1, count}, the bounding rectangle of the counting canvas units and their number; all 0 when none counts.
+int ofmk_affine_units(int h, int w, int H, int W, const ofmk_affine *geom, int out[5]) {
+    if (!geom || !out) return fail(OFMK_E_ARG, "null pointer%s");
+    if (int rc = check_leak_dims(h, w)) return rc;
+    if (H < 1 || W < 1 || (long long)H * W >= (1LL << 28)) return fail(OFMK_E_ARG, "canvas H, W must be positive with H*W < 2^28%s");
+    AffineMap m;
+    if (int rc = check_affine_map(geom, m)) return rc;
+    affine_rect(m, h, w, H, W, out);
+    return OFMK_OK;
+}
+
+// The leak resampled onto the canvas rectangle [oy, oy + Hout) x [ox, ox + Wout): u8 [n][Hout][Wout][3], every byte written.
+int ofmk_warp_affine_rgb8(const uint8_t *in, int n, int h, int w, uint8_t *out, int Hout, int Wout, int oy, int ox, const ofmk_affine *geom,
+                          void *stream, const ofmk_opts *opts) {
+    if (int orc = check_opts(opts)) return orc;
+    if (n <= 0) return fail(OFMK_E_ARG, "n must be positive%s");
+    if (!in || !out || !geom) return fail(OFMK_E_ARG, "null pointer%s");
+    if (int rc = check_leak_dims(h, w)) return rc;
+    if (Hout < 1 || Wout < 1 || (long long)Hout * Wout >= (1LL << 28)) return fail(OFMK_E_ARG, "Hout, Wout must be positive with Hout*Wout < 2^28%s");
+    if (oy < 0 || ox < 0 || oy >= (1 << 28) || ox >= (1 << 28)) return fail(OFMK_E_ARG, "oy, ox must be in [0, 2^28)%s");
+    AffineWarpArgs a;
+    if (int rc = check_affine_map(geom, a.m)) return rc;
+    const Ctx cx = make_ctx(stream, opts);
+    a.h = h; a.w = w; a.Hout = Hout; a.Wout = Wout; a.oy = oy; a.ox = ox;
+    a.in_stride = (size_t)h * w * 3;
+    a.out_stride = (size_t)Hout * Wout * 3;
+    for_chunks(n, kMaxChunk, [&](int f0, int cf) {
+        ScopedTiming timing(KIND_SVD, cx);
+        OFMK_TIMED_LAUNCH(timing, warp_affine_rgb8_kernel, grid_2d(Hout * Wout, cf), dim3(kThreads), 0, cx.s, in + (size_t)f0 * a.in_stride,
+                          out + (size_t)f0 * a.out_stride, a);
+        return OFMK_OK;
+    });
+    HIP_TRY(hipGetLastError());
+    return OFMK_OK;
+}
+
+// scores[f][k] = sum of |unit metric| over the counting units of frame f warped by cands[k] (DEVICE memory, [K]); int64 [n][K],
+// cleared here whatever it held.  Candidates sit in gridDim.y and frames in gridDim.z, both in chunks of at most 65535.
+int ofmk_svd_affine_scores_rgb8(const uint8_t *in, int n, int h, int w, int H, int W, const ofmk_affine *cands, int K, const double *scales,
+                                int blk, long long *scores, void *stream, const ofmk_opts *opts) {
+    if (int orc = check_opts(opts)) return orc;
+    if (int rc = check_dims(n, H, W)) return rc;
+    if (int rc = check_leak_dims(h, w)) return rc;
+    if (!in || !cands || !scores) return fail(OFMK_E_ARG, "null pointer%s");
+    if (K < 1) return fail(OFMK_E_ARG, "K must be at least 1%s");
+    if ((long long)n * K >= (1LL << 40)) return fail(OFMK_E_ARG, "n * K must be < 2^40%s");
+    SvdArgs sa;
+    if (int rc = check_resync_scales(sa, scales, blk, true)) return rc;
+    const Ctx cx = make_ctx(stream, opts);
+    HIP_TRY(launch_zero(scores, (size_t)n * K * sizeof(long long), cx.s));
+    AffineScoreArgs a;
+    a.h = h; a.w = w;
+    a.rows = H / 8; a.cols = W / 8;
+    a.tiles_x = (a.cols + kAffineTile - 1) / kAffineTile;
+    a.K = K;
+    a.frame_stride = (size_t)h * w * 3;
+    a.scale = sa.scales[1];
+    const long long tiles = (long long)a.tiles_x * ((a.rows + kAffineTile - 1) / kAffineTile);
+    const AffineMap *dc = reinterpret_cast<const AffineMap *>(cands);
+    for_chunks(K, kMaxChunk, [&](int k0, int ck) {
+        const long long room = (1LL << 30) / (tiles * ck);                       // workgroups per launch stay below 2^30
+        const int cap = room < 1 ? 1 : room > kMaxChunk ? kMaxChunk : (int)room;
+        return for_chunks(n, cap, [&](int f0, int cf) {
+            ScopedTiming timing(KIND_SVD, cx);
+            OFMK_TIMED_LAUNCH(timing, svd_affine_scores_rgb8_kernel, dim3((unsigned)tiles, (unsigned)ck, (unsigned)cf), dim3(kThreads), 0, cx.s,
+                              in + (size_t)f0 * a.frame_stride, dc + k0, a,
+                              reinterpret_cast<unsigned long long *>(scores) + (size_t)f0 * K + k0);
+            return OFMK_OK;
+        });
+    });
+    HIP_TRY(hipGetLastError());
+    return OFMK_OK;
+}
+
+// The soft read-out of the counting units of the leak warped by *geom (HOST memory), unit (i, j) into position (i * (W / 8) + j) mod L;
+// int64 [n][L], cleared here.  scales[1] <= 0 or no counting unit: all zeros.
+int ofmk_svd_detect_soft_affine_rgb8(const uint8_t *in, int n, int h, int w, int H, int W, const ofmk_affine *geom, int L, const double *scales,
+                                     int blk, long long *soft, void *stream, const ofmk_opts *opts) {
+    if (int orc = check_opts(opts)) return orc;
+    if (int rc = check_soft_args(in, n, H, W, L, soft)) return rc;
+    if (int rc = check_leak_dims(h, w)) return rc;
+    if (!geom) return fail(OFMK_E_ARG, "null pointer%s");
+    AffineReadArgs a;
+    if (int rc = check_affine_map(geom, a.m)) return rc;
+    SvdArgs sa;
+    if (int rc = check_resync_scales(sa, scales, blk, false)) return rc;
+    const Ctx cx = make_ctx(stream, opts);
+    HIP_TRY(launch_zero(soft, (size_t)n * L * sizeof(long long), cx.s));
+    int r[5];
+    affine_rect(a.m, h, w, H, W, r);
+    if (!(sa.scales[1] > 0.f) || r[4] == 0) return OFMK_OK;
+    a.h = h; a.w = w;
+    a.i0 = r[0]; a.j0 = r[2];
+    a.cols = r[3] - r[2];
+    a.nunits = (r[1] - r[0]) * a.cols;
+    a.canvas_cols = W / 8;
+    a.L = L;
+    a.frame_stride = (size_t)h * w * 3;
+    a.scale = sa.scales[1];
+    for_chunks(n, kMaxChunk, [&](int f0, int cf) {
+        ScopedTiming timing(KIND_SVD, cx);
+        AffineReadArgs ac = a;
+        ac.frames = cf;
+        ac.soft = soft + (size_t)f0 * L;
+        OFMK_TIMED_LAUNCH(timing, svd_soft_affine_rgb8_kernel, xcd_grid(a.nunits, cf), dim3(kThreads), 0, cx.s, in + (size_t)f0 * a.frame_stride, ac);
         return OFMK_OK;
     });
     HIP_TRY(hipGetLastError());

@@ -43,6 +43,15 @@ class Warp(C.Structure):
 
 _wp = C.POINTER(Warp)
 
+
+class Affine(C.Structure):
+    """ofmk_affine: the Q16 2x3 map canvas pixel (y, x) -> leak sample of the rotated-leak calls,
+    pos_y = ayy * y + ayx * x + by, pos_x = axy * y + axx * x + bx."""
+    _fields_ = [("ayy", C.c_int64), ("ayx", C.c_int64), ("by", C.c_int64), ("axy", C.c_int64), ("axx", C.c_int64), ("bx", C.c_int64)]
+
+
+_ap = C.POINTER(Affine)
+
 #: every symbol include/offmark_hip.h declares: name -> (restype, argtypes)
 SIGNATURES = {
     "ofmk_version": (_i32, []),
@@ -113,6 +122,10 @@ SIGNATURES = {
     "ofmk_warp_rgb8": (_i32, [_vp, _i32, _i32, _i32, _vp, _i32, _i32, _i32, _i32, _wp, _vp, _op]),
     "ofmk_svd_warp_scores_rgb8": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _dp, _i32, _vp, _vp, _op]),
     "ofmk_svd_detect_soft_warp_rgb8": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _wp, _i32, _dp, _i32, _vp, _vp, _op]),
+    "ofmk_affine_units": (_i32, [_i32, _i32, _i32, _i32, _ap, C.POINTER(_i32)]),
+    "ofmk_warp_affine_rgb8": (_i32, [_vp, _i32, _i32, _i32, _vp, _i32, _i32, _i32, _i32, _ap, _vp, _op]),
+    "ofmk_svd_affine_scores_rgb8": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _dp, _i32, _vp, _vp, _op]),
+    "ofmk_svd_detect_soft_affine_rgb8": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _ap, _i32, _dp, _i32, _vp, _vp, _op]),
     "ofmk_probe_xcc": (_i32, [_vp, _i32, _vp, _op]),
     "ofmk_hbm_copy": (_i32, [_vp, _vp, _sz, _vp]),
     "ofmk_hbm_read": (_i32, [_vp, _sz, _vp, _vp]),

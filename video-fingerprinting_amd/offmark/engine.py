@@ -679,6 +679,64 @@ class DctEngine:
                                                            self._o()))
         return soft
 
+    # -- rotated leaks: the same warp under a 2x3 affine map (build extension; blk 4, channel 1; offmark.resync) ------------------
+    @staticmethod
+    def _affine_geom(geom):
+        g = [int(v) for v in np.asarray(geom).reshape(-1)]
+        if len(g) != 6:
+            raise ValueError("an affine geometry is (ayy, ayx, by, axy, axx, bx) in Q16")
+        return _hip.Affine(*g)
+
+    def warp_affine(self, frames, geom, out_hw, origin=(0, 0), out=None):
+        """``warp`` under ``geom`` = (ayy, ayx, by, axy, axx, bx) (Q16; offmark.resync.affine_of_rotation): canvas pixel (y, x) reads
+        the leak at (ayy * y + ayx * x + by, axy * y + axx * x + bx).  uint8 [n, Hout, Wout, 3], 0 outside the leak
+        (include/offmark_hip.h: ofmk_affine)."""
+        t = self.torch
+        n, h, w = self._check_frames(frames, t.uint8)
+        Hout, Wout = (int(v) for v in out_hw)
+        out = self._out(out, frames, (n, Hout, Wout, 3))
+        g = self._affine_geom(geom)
+        _hip.check(self.lib.ofmk_warp_affine_rgb8(frames.data_ptr(), n, h, w, out.data_ptr(), Hout, Wout, int(origin[0]), int(origin[1]),
+                                                  C.byref(g), _hip.current_stream(), self._o()))
+        return out
+
+    def affine_units(self, leak_hw, canvas_hw, geom):
+        """(i0, i1, j0, j1, count): the bounding rectangle of the canvas units whose 64 pixels all fall inside the leak under
+        ``geom``, and how many there are (they are convex, not a rectangle); all 0 when none does.  Host only."""
+        r = (C.c_int * 5)()
+        g = self._affine_geom(geom)
+        _hip.check(self.lib.ofmk_affine_units(int(leak_hw[0]), int(leak_hw[1]), int(canvas_hw[0]), int(canvas_hw[1]), C.byref(g), r))
+        return tuple(r)
+
+    def svd_affine_scores(self, frames, canvas_hw, cands, scale=15, scales=None, blk=4, scores=None):
+        """svd_warp_scores over affine candidates: ``cands`` int64 [K, 6] rows (ayy, ayx, by, axy, axx, bx), a tensor on this
+        device or an array (copied there).  int64 [n, K]; a candidate out of range or without a counting unit scores 0."""
+        t = self.torch
+        n, h, w = self._check_frames(frames, t.uint8)
+        if not isinstance(cands, t.Tensor):
+            cands = t.from_numpy(np.ascontiguousarray(np.asarray(cands, dtype=np.int64)))
+        cands = cands.to(device=self.device, dtype=t.int64).contiguous()
+        if cands.dim() != 2 or cands.shape[1] != 6 or cands.shape[0] < 1:
+            raise ValueError("cands must be int64 [K, 6] with K >= 1")
+        K = int(cands.shape[0])
+        scores = self._soft(scores, n, K)
+        _hip.check(self.lib.ofmk_svd_affine_scores_rgb8(frames.data_ptr(), n, h, w, int(canvas_hw[0]), int(canvas_hw[1]), cands.data_ptr(), K,
+                                                        _hip.scales3(scale, scales), int(blk), scores.data_ptr(), _hip.current_stream(),
+                                                        self._o()))
+        return scores
+
+    def svd_detect_soft_affine(self, frames, canvas_hw, geom, L, scale=15, scales=None, blk=4, soft=None):
+        """svd_detect_soft_warp under an affine ``geom``: the counting units only, unit (i, j) at (i * (W // 8) + j) % L.
+        int64 [n, L]; equals warp_affine + svd_detect_soft restricted to the counting units."""
+        t = self.torch
+        n, h, w = self._check_frames(frames, t.uint8)
+        soft = self._soft(soft, n, L)
+        g = self._affine_geom(geom)
+        _hip.check(self.lib.ofmk_svd_detect_soft_affine_rgb8(frames.data_ptr(), n, h, w, int(canvas_hw[0]), int(canvas_hw[1]), C.byref(g),
+                                                             int(L), _hip.scales3(scale, scales), int(blk), soft.data_ptr(),
+                                                             _hip.current_stream(), self._o()))
+        return soft
+
     def svd_embed_detect(self, frames, wm, L, scale=15, wm_row=None, out=None, want_bits=False, scales=None, blk=4, counts=None,
                          partial=False):
         t = self.torch

@@ -72,6 +72,15 @@ class DwtDctSvdDecoder:
         (engine.svd_detect_soft_warp)."""
         return self.engine.svd_detect_soft_warp(frames, canvas_hw, geom, L, scales=self._scales, blk=self.blk)
 
+    # -- rotated leaks (build extension; blk 4 only: offmark.resync.read_rescaled_leak with [K, 6] geometries) --------------------
+    def affine_scores_u8(self, frames, canvas_hw, cands):
+        """warp_scores_u8 over affine candidates, int64 [K, 6] (engine.svd_affine_scores)."""
+        return self.engine.svd_affine_scores(frames, canvas_hw, cands, scales=self._scales, blk=self.blk)
+
+    def decode_soft_affine_u8(self, frames, canvas_hw, geom, L):
+        """decode_soft_warp_u8 at an affine ``geom`` of six (engine.svd_detect_soft_affine)."""
+        return self.engine.svd_detect_soft_affine(frames, canvas_hw, geom, L, scales=self._scales, blk=self.blk)
+
     def sync_scores_planes_yuv420(self, planes, height, width, layout="i420"):
         """planes: CUDA uint8 [n, 1.5*H*W] (I420 or NV12), even H, W >= 8 -> int64 [n, 64] on device: sync_scores_u8's sums at the
         phases with even py and px, 0 elsewhere -- an odd crop offset does not exist on 4:2:0 planes (engine.svd_sync_scores_yuv420)."""

@@ -38,7 +38,13 @@ candidate geometries (``crop_candidates``) in one fused call, ``best_geometry`` 
 reads at one geometry: ``read_rescaled_leak``.  The score is as sharp as the phase search -- one crop edge off by a pixel falls to
 the unmarked level, rows and columns do not separate -- and only DwtDctSvd has a search: the DCT codec's C21 is small on smooth
 resampled content whether marked or not, so it reads at a geometry known from the sizes or found by other means.
-Rotation, shear, 4:2:0 planes under a rescale and blk 8 are not handled.
+ROTATED leaks (and sheared, flipped or turned ones; interleaved RGB, DwtDctSvd only) are the same recipe under a 2x3 integer
+affine map: ``affine_of_rotation`` / ``affine_of_warp`` make one, ``affine_units`` gives the counting units (convex, no longer a
+rectangle), ``rotation_candidates`` a list, and ``best_geometry`` / ``read_rescaled_leak`` take [K, 6] lists as well as [K, 4]
+(``DwtDctSvdDecoder.affine_scores_u8`` / ``decode_soft_affine_u8``).  The parameters have to be right all at once: an angle off by
+0.25 degrees already falls to the unmarked level.  The DCT codec has no affine read-out: its frame mean and masks would have to
+come from a non-rectangular set of blocks.
+4:2:0 planes under any resampling, blk 8, perspective and search strategies beyond scoring a given list are not handled.
 """
 from __future__ import annotations
 
@@ -248,17 +254,91 @@ def crop_candidates(canvas_hw, leak_hw, tops, lefts, heights, widths) -> np.ndar
     return np.asarray(out, dtype=np.int64).reshape(-1, 4)
 
 
+# ---- rotated leaks: the same warp under a 2x3 affine map ------------------------------------------------------------------------
+AFFINE_MAX_A, AFFINE_MIN_DET, AFFINE_MAX_B = 1 << 20, 1 << 24, 1 << 48
+
+
+def _affine_ok(g) -> bool:
+    ayy, ayx, by, axy, axx, bx = (int(v) for v in g)
+    return (all(abs(a) <= AFFINE_MAX_A for a in (ayy, ayx, axy, axx)) and abs(by) <= AFFINE_MAX_B and abs(bx) <= AFFINE_MAX_B
+            and abs(ayy * axx - ayx * axy) >= AFFINE_MIN_DET)
+
+
+def affine_of_warp(geom4) -> tuple:
+    """(ayy, ayx, by, axy, axx, bx) of a warp geometry (ay, by, ax, bx): zero off-diagonal terms, the same warp byte for byte."""
+    ay, by, ax, bx = (int(v) for v in np.asarray(geom4).reshape(-1))
+    return ay, 0, by, 0, ax, bx
+
+
+def affine_of_rotation(canvas_hw, leak_hw, angle_deg: float, scale: float = 1.0, shift=(0.0, 0.0)) -> tuple:
+    """(ayy, ayx, by, axy, axx, bx), Q16: the map canvas pixel -> leak sample for a leak whose pixel p = (y, x) shows the canvas at
+    scale * R(angle) * (p - c_leak) + c_canvas + shift, with R(a) = [[cos a, -sin a], [sin a, cos a]] on (y, x) vectors and c the
+    index centres ((H - 1) / 2, (W - 1) / 2).  It is the inverse map, p = R(-angle) / scale * (q - c_canvas - shift) + c_leak,
+    each coefficient rounded once to Q16 (float64, to nearest); the integers are the definition from there on."""
+    a = np.deg2rad(float(angle_deg))
+    m = np.array([[np.cos(a), np.sin(a)], [-np.sin(a), np.cos(a)]]) / float(scale)
+    cl = np.array([(int(leak_hw[0]) - 1) / 2.0, (int(leak_hw[1]) - 1) / 2.0])
+    cc = np.array([(int(canvas_hw[0]) - 1) / 2.0 + float(shift[0]), (int(canvas_hw[1]) - 1) / 2.0 + float(shift[1])])
+    b = cl - m @ cc
+    q = [int(np.rint(v * WARP_ONE)) for v in (m[0, 0], m[0, 1], b[0], m[1, 0], m[1, 1], b[1])]
+    return tuple(q)
+
+
+def affine_units(leak_hw, canvas_hw, geom) -> np.ndarray:
+    """bool [H // 8, W // 8]: the canvas units whose 64 pixels all fall inside the leak under the affine ``geom``.  Positions are
+    affine and the inside set is an intersection of half-planes, so a unit counts iff its four corner pixels are inside; the
+    counting units are convex, not a rectangle.  Bounding rectangle and count equal the library's ofmk_affine_units."""
+    g = tuple(int(v) for v in np.asarray(geom).reshape(-1))
+    if len(g) != 6 or not _affine_ok(g):
+        raise ValueError("an affine geometry is (ayy, ayx, by, axy, axx, bx) with coefficients in [-2^20, 2^20], |b| <= 2^48 and "
+                         "|ayy * axx - ayx * axy| >= 2^24")
+    ayy, ayx, by, axy, axx, bx = g
+    h, w = int(leak_hw[0]), int(leak_hw[1])
+    i = 8 * np.arange(int(canvas_hw[0]) // 8, dtype=np.int64)[:, None]
+    j = 8 * np.arange(int(canvas_hw[1]) // 8, dtype=np.int64)[None, :]
+    ok = np.ones((i.shape[0], j.shape[1]), bool)
+    for dy in (0, 7):
+        for dx in (0, 7):
+            y0, x0 = (ayy * (i + dy) + ayx * (j + dx) + by) >> 16, (axy * (i + dy) + axx * (j + dx) + bx) >> 16
+            ok &= (y0 >= 0) & (y0 <= h - 1) & (x0 >= 0) & (x0 <= w - 1)
+    return ok
+
+
+def rotation_candidates(canvas_hw, leak_hw, angles, scales, shifts_y, shifts_x) -> np.ndarray:
+    """int64 [K, 6]: affine_of_rotation of every (angle, scale, shift_y, shift_x) of the four lists' product, in that nesting
+    order, whose map is in the affine warp's range."""
+    out = []
+    for angle in angles:
+        for scale in scales:
+            for sy in shifts_y:
+                for sx in shifts_x:
+                    g = affine_of_rotation(canvas_hw, leak_hw, angle, scale, (sy, sx))
+                    if _affine_ok(g):
+                        out.append(g)
+    return np.asarray(out, dtype=np.int64).reshape(-1, 6)
+
+
+def _geometries(geometries) -> np.ndarray:
+    """int64 [K, 4] warp geometries or [K, 6] affine ones (a single geometry of six numbers is [1, 6])."""
+    g = np.asarray(_host(geometries), dtype=np.int64)
+    return g.reshape(-1, 6) if g.shape[-1:] == (6,) else g.reshape(-1, 4)
+
+
 def best_geometry(scores, cands, leak_hw, canvas_hw) -> dict:
-    """scores: [K] or [n, K] sums of |soft metric| per candidate geometry (rows are added); cands: int64 [K, 4] ->
+    """scores: [K] or [n, K] sums of |soft metric| per candidate geometry (rows are added); cands: int64 [K, 4] (or [K, 6] affine
+    geometries: units from affine_units) ->
     dict(index, geometry=(ay, by, ax, bx), normalised=float64 [K], contrast=top / second).  normalised = score / (2^14 * counting
     units * frames): about 0.8 at a marked leak's true geometry (bilinear resampling twice costs the rest), the unmarked level
     (0.6-0.7) elsewhere; candidates without a counting unit are excluded (0 there).  No verdict: the caller judges ``contrast``
     (inf when one candidate at most has units or the second-best scores 0)."""
-    cands = np.asarray(cands, dtype=np.int64).reshape(-1, 4)
+    cands = _geometries(cands)
     K = cands.shape[0]
     s = np.asarray(scores, dtype=np.int64).reshape(-1, K)
     units = np.empty(K, np.int64)
     for k in range(K):
+        if cands.shape[1] == 6:
+            units[k] = int(affine_units(leak_hw, canvas_hw, cands[k]).sum())
+            continue
         i0, i1, j0, j1 = warp_units(leak_hw, canvas_hw, cands[k])
         units[k] = (i1 - i0) * (j1 - j0)
     have = units > 0
@@ -277,19 +357,26 @@ def read_rescaled_leak(decoder, frames, segment_of_frame, canvas_hw, candidates,
     nothing is searched.  All frames are then read at that geometry, summed per segment, and each segment takes the candidate
     that correlates best with the position rotation fixed at 0 (canvas coordinates leave none).  -> dict(geometry, index,
     contrast, normalised (None, None without a search), segments, soft_by_segment, base (0), picks, score, runner_up_score
-    (None), ambiguous).  No verdict on ``contrast``."""
+    (None), ambiguous).  No verdict on ``contrast``.
+    ``geometries`` may also be int64 [K, 6] affine geometries (rotation_candidates / affine_of_rotation): the search is then
+    decoder.affine_scores_u8, the read-out decoder.decode_soft_affine_u8 and the units come from affine_units.  Only
+    DwtDctSvdDecoder has them: a DctDecoder with a 6-column geometry raises ValueError."""
     leak_hw = (int(frames.shape[1]), int(frames.shape[2]))
     canvas_hw = (int(canvas_hw[0]), int(canvas_hw[1]))
-    geoms = np.asarray(_host(geometries), dtype=np.int64).reshape(-1, 4)
+    geoms = _geometries(geometries)
     if geoms.shape[0] < 1:
         raise ValueError("geometries must hold at least one (ay, by, ax, bx)")
+    affine = geoms.shape[1] == 6
+    search, read = ("affine_scores_u8", "decode_soft_affine_u8") if affine else ("warp_scores_u8", "decode_soft_warp_u8")
+    if affine and not hasattr(decoder, read):
+        raise ValueError(f"{type(decoder).__name__} does not read at an affine geometry ({read}): only DwtDctSvd does")
     if geoms.shape[0] > 1:
-        if not hasattr(decoder, "warp_scores_u8"):
-            raise ValueError(f"{type(decoder).__name__} has no geometry search (warp_scores_u8): give the one known geometry")
-        found = best_geometry(_host(decoder.warp_scores_u8(frames[:max(1, int(search_frames))], canvas_hw, geoms)), geoms, leak_hw, canvas_hw)
+        if not hasattr(decoder, search):
+            raise ValueError(f"{type(decoder).__name__} has no geometry search ({search}): give the one known geometry")
+        found = best_geometry(_host(getattr(decoder, search)(frames[:max(1, int(search_frames))], canvas_hw, geoms)), geoms, leak_hw, canvas_hw)
     else:
         found = dict(index=0, geometry=tuple(int(v) for v in geoms[0]), normalised=None, contrast=None)
-    soft = decoder.decode_soft_warp_u8(frames, canvas_hw, found["geometry"], L)
+    soft = getattr(decoder, read)(frames, canvas_hw, found["geometry"], L)
     out = _align_by_segment(soft, segment_of_frame, candidates, key, bases=(0,))
     out.update(geometry=found["geometry"], index=found["index"], contrast=found["contrast"], normalised=found["normalised"])
     return out
