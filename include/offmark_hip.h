@@ -613,7 +613,22 @@ int ofmk_svd_detect_soft_warp_rgb8(const uint8_t *in, int n, int h, int w, int H
  * ofmk_svd_detect_soft_affine_rgb8: as ofmk_svd_detect_soft_warp_rgb8 -- counting unit (i, j) adds m into position
  *   (i * (W/8) + j) mod L; soft is cleared by the call; scales[1] <= 0 or no counting unit: all zeros.  Equal, integer for integer,
  *   to ofmk_warp_affine_rgb8 of the canvas followed by the soft read-out of the counting units at their canvas positions.
- * The three device calls allocate nothing, synchronise nothing and are graph capturable; all three are timed as kind 4 (svd);
+ * ofmk_svd_affine_phase_scores_rgb8: the DENSE SHIFT SEARCH, for a leak that was rotated or rescaled and then cropped off-centre, so
+ *   that its translation is unknown.  A shift of the canvas by whole pixels (py, px) is an exact integer change of a map's offsets,
+ *       g (+) (py, px):   by' = by + ayy*py + ayx*px    bx' = bx + axy*py + axx*px
+ *   and the call scores all 64 shifts by 0..7 px of every candidate: scores[f][k][8*py + px] (device int64 [n][K][64]) is the score
+ *   ofmk_svd_affine_scores_rgb8 gives frame f under cands[k] (+) (py, px) on the same canvas H x W, integer for integer: the sum of
+ *   |m| over units (i, j), i < H/8, j < W/8, whose canvas pixels are (py + 8i + r, px + 8j + c); a unit counts iff its four corner
+ *   pixels are inside the leak.  Canvas coordinates are an index space: a shifted unit may reach past row H or column W.
+ *   units[k][8*py + px] (device int64 [K][64], may be NULL) is the count ofmk_affine_units(h, w, H, W, cands[k] (+) (py, px)) returns,
+ *   written once per call.  Both outputs are cleared by the call.  A candidate is in range iff all 64 shifted maps pass ofmk_affine's
+ *   rules (the linear part is shared: a condition on by, bx); one that is not scores 0 in all 64 entries and has 0 units (the list is
+ *   device memory and is not read on the host).  Shifts by whole units need no entry: they rotate the payload positions by a
+ *   constant, which offmark.resync.align_segments resolves; sub-pixel shifts do (offmark.resync.subpixel_shifts).
+ *   A workgroup owns 32 x 32 canvas pixel origins of one candidate and one frame: it warps the 39 x 39 pixels they cover once, stages
+ *   their dense LL plane in LDS as ofmk_svd_sync_scores_rgb8 does and runs one solver per origin that counts, so a candidate's
+ *   pixels are warped once instead of once per shift.  Arguments, chunking and flags as ofmk_svd_affine_scores_rgb8.
+ * The four device calls allocate nothing, synchronise nothing and are graph capturable; all four are timed as kind 4 (svd);
  * OFMK_F_PARTIAL_COUNTS and the tile-order flags are ignored.  Argument checks: those of the ofmk_warp counterparts. */
 typedef struct ofmk_affine { int64_t ayy, ayx, by, axy, axx, bx; } ofmk_affine;
 int ofmk_affine_units(int h, int w, int H, int W, const ofmk_affine *geom, int out[5]);
@@ -621,6 +636,9 @@ int ofmk_warp_affine_rgb8(const uint8_t *in, int n, int h, int w, uint8_t *out, 
                           const ofmk_affine *geom, void *stream, const ofmk_opts *opts);
 int ofmk_svd_affine_scores_rgb8(const uint8_t *in, int n, int h, int w, int H, int W, const ofmk_affine *cands, int K,
                                 const double *scales, int blk, long long *scores, void *stream, const ofmk_opts *opts);
+int ofmk_svd_affine_phase_scores_rgb8(const uint8_t *in, int n, int h, int w, int H, int W, const ofmk_affine *cands, int K,
+                                      const double *scales, int blk, long long *scores, long long *units, void *stream,
+                                      const ofmk_opts *opts);
 int ofmk_svd_detect_soft_affine_rgb8(const uint8_t *in, int n, int h, int w, int H, int W, const ofmk_affine *geom, int L,
                                      const double *scales, int blk, long long *soft, void *stream, const ofmk_opts *opts);
 

@@ -52,6 +52,7 @@
 #include "planar_resync_kernels.hiph"
 #include "warp_kernels.hiph"
 #include "affine_kernels.hiph"
+#include "affine_phase_kernels.hiph"
 
 namespace {
 
@@ -1897,6 +1898,50 @@ int ofmk_svd_affine_scores_rgb8(const uint8_t *in, int n, int h, int w, int H, i
             OFMK_TIMED_LAUNCH(timing, svd_affine_scores_rgb8_kernel, dim3((unsigned)tiles, (unsigned)ck, (unsigned)cf), dim3(kThreads), 0, cx.s,
                               in + (size_t)f0 * a.frame_stride, dc + k0, a,
                               reinterpret_cast<unsigned long long *>(scores) + (size_t)f0 * K + k0);
+            return OFMK_OK;
+        });
+    });
+    HIP_TRY(hipGetLastError());
+    return OFMK_OK;
+}
+
+// The dense shift search (affine_phase_kernels.hiph): scores[f][k][8 py + px] = what ofmk_svd_affine_scores_rgb8 gives frame f under
+// cands[k] (+) (py, px), int64 [n][K][64]; units[k][8 py + px] = ofmk_affine_units' count under that map, int64 [K][64] or NULL, added
+// by the launches that hold the call's first frame only.  Both are cleared here whatever they held.  Chunks as above.
+int ofmk_svd_affine_phase_scores_rgb8(const uint8_t *in, int n, int h, int w, int H, int W, const ofmk_affine *cands, int K, const double *scales,
+                                      int blk, long long *scores, long long *units, void *stream, const ofmk_opts *opts) {
+    if (int orc = check_opts(opts)) return orc;
+    if (int rc = check_dims(n, H, W)) return rc;
+    if (int rc = check_leak_dims(h, w)) return rc;
+    if (!in || !cands || !scores) return fail(OFMK_E_ARG, "null pointer%s");
+    if (K < 1) return fail(OFMK_E_ARG, "K must be at least 1%s");
+    if ((long long)n * K >= (1LL << 40)) return fail(OFMK_E_ARG, "n * K must be < 2^40%s");
+    SvdArgs sa;
+    if (int rc = check_resync_scales(sa, scales, blk, true)) return rc;
+    const Ctx cx = make_ctx(stream, opts);
+    HIP_TRY(launch_zero(scores, (size_t)n * K * 64 * sizeof(long long), cx.s));
+    if (units) HIP_TRY(launch_zero(units, (size_t)K * 64 * sizeof(long long), cx.s));
+    AffinePhaseArgs a;
+    a.h = h; a.w = w;
+    a.oh = 8 * (H / 8); a.ow = 8 * (W / 8);
+    a.rects_x = (a.ow + kPhaseRect - 1) / kPhaseRect;
+    a.K = K;
+    a.count_units = 0;
+    a.frame_stride = (size_t)h * w * 3;
+    a.scale = sa.scales[1];
+    const long long rects = (long long)a.rects_x * ((a.oh + kPhaseRect - 1) / kPhaseRect);
+    const AffineMap *dc = reinterpret_cast<const AffineMap *>(cands);
+    unsigned long long *du = reinterpret_cast<unsigned long long *>(units);
+    for_chunks(K, kMaxChunk, [&](int k0, int ck) {
+        const long long room = (1LL << 30) / (rects * ck);                       // workgroups per launch stay below 2^30
+        const int cap = room < 1 ? 1 : room > kMaxChunk ? kMaxChunk : (int)room;
+        return for_chunks(n, cap, [&](int f0, int cf) {
+            ScopedTiming timing(KIND_SVD, cx);
+            AffinePhaseArgs ac = a;
+            ac.count_units = units && f0 == 0;                                   // once per call: the chunk with the first frame
+            OFMK_TIMED_LAUNCH(timing, svd_affine_phase_scores_rgb8_kernel, dim3((unsigned)rects, (unsigned)ck, (unsigned)cf), dim3(kThreads), 0, cx.s,
+                              in + (size_t)f0 * a.frame_stride, dc + k0, ac,
+                              reinterpret_cast<unsigned long long *>(scores) + ((size_t)f0 * K + k0) * 64, units ? du + (size_t)k0 * 64 : du);
             return OFMK_OK;
         });
     });

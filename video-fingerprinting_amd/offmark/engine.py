@@ -725,6 +725,27 @@ class DctEngine:
                                                         self._o()))
         return scores
 
+    def svd_affine_phase_scores(self, frames, canvas_hw, cands, scale=15, scales=None, blk=4, scores=None, units=None):
+        """The dense shift search: svd_affine_scores of every candidate under all 64 whole-pixel shifts (py, px) in 0..7 of the
+        canvas (offmark.resync.shift_affine), for about the price of one.  -> (scores int64 [n, K, 64], units int64 [K, 64]), at
+        index 8 * py + px: the sum of |unit metric| and the number of counting units (affine_units' count) under the shifted
+        geometry.  A candidate out of range under any of its 64 shifts has zeros throughout.  ``units=False`` skips the counts
+        (None is returned for them).  offmark.resync.best_shifted_geometry reads the result."""
+        t = self.torch
+        n, h, w = self._check_frames(frames, t.uint8)
+        if not isinstance(cands, t.Tensor):
+            cands = t.from_numpy(np.ascontiguousarray(np.asarray(cands, dtype=np.int64)))
+        cands = cands.to(device=self.device, dtype=t.int64).contiguous()
+        if cands.dim() != 2 or cands.shape[1] != 6 or cands.shape[0] < 1:
+            raise ValueError("cands must be int64 [K, 6] with K >= 1")
+        K = int(cands.shape[0])
+        scores = self._soft(scores, K, 64, copies=n)
+        units = None if units is False else self._soft(units, K, 64)
+        _hip.check(self.lib.ofmk_svd_affine_phase_scores_rgb8(frames.data_ptr(), n, h, w, int(canvas_hw[0]), int(canvas_hw[1]), cands.data_ptr(),
+                                                              K, _hip.scales3(scale, scales), int(blk), scores.data_ptr(), _hip.ptr(units),
+                                                              _hip.current_stream(), self._o()))
+        return scores, units
+
     def svd_detect_soft_affine(self, frames, canvas_hw, geom, L, scale=15, scales=None, blk=4, soft=None):
         """svd_detect_soft_warp under an affine ``geom``: the counting units only, unit (i, j) at (i * (W // 8) + j) % L.
         int64 [n, L]; equals warp_affine + svd_detect_soft restricted to the counting units."""

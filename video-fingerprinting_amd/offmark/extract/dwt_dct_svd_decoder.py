@@ -77,6 +77,11 @@ class DwtDctSvdDecoder:
         """warp_scores_u8 over affine candidates, int64 [K, 6] (engine.svd_affine_scores)."""
         return self.engine.svd_affine_scores(frames, canvas_hw, cands, scales=self._scales, blk=self.blk)
 
+    def affine_phase_scores_u8(self, frames, canvas_hw, cands):
+        """affine_scores_u8 of every candidate under all 64 whole-pixel shifts of the canvas: (scores int64 [n, K, 64], units
+        int64 [K, 64]) at index 8 * py + px (engine.svd_affine_phase_scores; offmark.resync.best_shifted_geometry)."""
+        return self.engine.svd_affine_phase_scores(frames, canvas_hw, cands, scales=self._scales, blk=self.blk)
+
     def decode_soft_affine_u8(self, frames, canvas_hw, geom, L):
         """decode_soft_warp_u8 at an affine ``geom`` of six (engine.svd_detect_soft_affine)."""
         return self.engine.svd_detect_soft_affine(frames, canvas_hw, geom, L, scales=self._scales, blk=self.blk)

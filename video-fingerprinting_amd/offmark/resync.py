@@ -44,7 +44,28 @@ rectangle), ``rotation_candidates`` a list, and ``best_geometry`` / ``read_resca
 (``DwtDctSvdDecoder.affine_scores_u8`` / ``decode_soft_affine_u8``).  The parameters have to be right all at once: an angle off by
 0.25 degrees already falls to the unmarked level.  The DCT codec has no affine read-out: its frame mean and masks would have to
 come from a non-rectangular set of blocks.
-4:2:0 planes under any resampling, blk 8, perspective and search strategies beyond scoring a given list are not handled.
+ROTATED-AND-CROPPED leaks (rotated or rescaled, then cropped off-centre: the normal case) have an unknown translation, and that
+is the one part of a geometry that needs no list.  A shift of the canvas by whole pixels (py, px) is an exact integer change of
+the map's offsets, ``shift_affine``: by' = by + ayy * py + ayx * px, bx' = bx + axy * py + axx * px.  The shifts by 0..7 px are
+the 64 phases of the unit grid on the warped canvas -- ``DwtDctSvdDecoder.affine_phase_scores_u8`` scores all 64 of every
+candidate in one call, ``best_shifted_geometry`` ranks the K x 64 entries -- and shifts by whole units only rotate the payload
+positions, which ``align_segments`` resolves as for cropped leaks: ``read_transformed_leak``.  What still has to be listed is the
+LINEAR part (angle, scale) and the SUB-PIXEL shift (``subpixel_shifts``).  Measured on the NumPy statement (tests/_affine_phase.py:
+the 72x104 recipe rotated by 2 degrees and cropped, first 4 frames):
+  * rows 7:63 / columns 5:95: the truth scores 0.740 normalised at phase (1, 2) on 65 units, its second phase 0.677, angles off by
+    0.25 / 0.5 degrees and scale +-1 % at most 0.706 over all phases, the unmarked sources at most 0.699; copies [1, 0, 1] with
+    an alignment score of 7.85 M against 4.46 M for the runner-up base;
+  * rows 7:64 / columns 5:96 (odd sizes move the index centre by half a pixel): whole-pixel shifts alone reach 0.691, the
+    unmarked level, and return wrong copies; with the sub-pixel shift (0.5, 0.5) the truth scores 0.742 on 73 units against at
+    most 0.695 elsewhere and the copies come out (9.28 M against 5.04 M).  Hence the 2 x 2 half-pixel sub-lattice;
+  * the fall-off: the score's peak is about a quarter of a pixel wide -- 0.754 at the exact translation, about 0.70 at 0.06 to
+    0.125 px, the unmarked level from 0.19 px on, and at 0.25 to 0.5 px the best of all 64 phases is 0.67-0.69 -- and a
+    quarter-pixel lattice gains nothing on the recipe.  The half-pixel lattice is enough for whole-pixel crops of a frame rotated
+    about its centre (the translation is then within about 0.1 px of a multiple of half a pixel); it is NOT a cover of an
+    arbitrary translation, which takes subpixel_shifts(8).
+The contrasts are thin (about 1.05 between candidates, 1.07-1.09 between phases on 4 small frames): no verdict is given.
+4:2:0 planes under any resampling, blk 8, perspective, the DCT codec under an affine map and a search of the linear part itself
+(anything beyond scoring a given list of linear parts and sub-pixel shifts) are not handled.
 """
 from __future__ import annotations
 
@@ -379,4 +400,88 @@ def read_rescaled_leak(decoder, frames, segment_of_frame, canvas_hw, candidates,
     soft = getattr(decoder, read)(frames, canvas_hw, found["geometry"], L)
     out = _align_by_segment(soft, segment_of_frame, candidates, key, bases=(0,))
     out.update(geometry=found["geometry"], index=found["index"], contrast=found["contrast"], normalised=found["normalised"])
+    return out
+
+
+# ---- rotated (or rescaled) AND cropped leaks: the translation leaves the candidate list ---------------------------------------------
+def shift_affine(geom, py: int, px: int):
+    """g (+) (py, px): the affine geometry that reads, at canvas pixel (y, x), what ``geom`` reads at canvas pixel (y + py, x + px) --
+    by' = by + ayy * py + ayx * px, bx' = bx + axy * py + axx * px, exact in Python integers.  One geometry of six -> a tuple of six
+    ints; an int64 [K, 6] array -> an int64 [K, 6] array."""
+    g = np.asarray(_host(geom))
+    py, px = int(py), int(px)
+
+    def one(v):
+        ayy, ayx, by, axy, axx, bx = (int(c) for c in v)
+        return ayy, ayx, by + ayy * py + ayx * px, axy, axx, bx + axy * py + axx * px
+
+    if g.ndim == 1 and g.size == 6:
+        return one(g)
+    if g.ndim != 2 or g.shape[1] != 6:
+        raise ValueError("an affine geometry is (ayy, ayx, by, axy, axx, bx), or an int64 [K, 6] array of them")
+    return np.asarray([one(v) for v in g], dtype=np.int64).reshape(-1, 6)
+
+
+def subpixel_shifts(s: int = 2) -> tuple:
+    """(0, 1/s, ..., (s - 1)/s): the shifts in [0, 1) px of one axis; given to rotation_candidates as both ``shifts_y`` and
+    ``shifts_x`` they make the s x s sub-pixel lattice the dense shift search needs on top of its 64 whole-pixel phases.  Module
+    docstring: whole pixels alone (s = 1) are not enough; s = 2 reads whole-pixel crops of a frame rotated about its centre; the
+    score's peak is about a quarter of a pixel wide, so an arbitrary translation takes s = 8."""
+    s = int(s)
+    if s < 1:
+        raise ValueError("s must be at least 1")
+    return tuple(k / s for k in range(s))
+
+
+def best_shifted_geometry(scores, units, cands) -> dict:
+    """scores: [K, 64] or [n, K, 64] sums of |soft metric| per candidate and whole-pixel shift (rows are added); units: [K, 64]
+    counting units behind each entry (both from decoder.affine_phase_scores_u8); cands: int64 [K, 6] ->
+    dict(index, phase=(py, px), geometry = shift_affine(cands[index], py, px), normalised=float64 [K, 64] = score / (2^14 * units *
+    frames), 0 where units is 0; contrast = best / the best entry of any OTHER candidate; phase_contrast = best / the second-best
+    phase of the SAME candidate; each inf when there is no such entry or it scores 0).  No verdict: the caller judges the two
+    contrasts (about 1.05 and 1.07-1.09 on four small frames of the test recipe: thin)."""
+    cands = _geometries(cands)
+    K = cands.shape[0]
+    if cands.shape[1] != 6:
+        raise ValueError("cands must be int64 [K, 6] affine geometries")
+    s = np.asarray(_host(scores), dtype=np.int64).reshape(-1, K * 64)
+    u = np.asarray(_host(units), dtype=np.int64).reshape(K * 64)
+    have = u > 0
+    if not have.any():
+        raise ValueError("no candidate geometry has a counting unit under any shift")
+    norm, top, _ = _rank(s, u, have)
+    norm = norm.reshape(K, 64)
+    index, phase = top // 64, ((top % 64) // 8, top % 8)
+
+    def over(rest):
+        return float(norm[index, top % 64] / rest.max()) if rest.size and rest.max() > 0 else float("inf")
+
+    return dict(index=index, phase=phase, geometry=shift_affine(cands[index], *phase), normalised=norm,
+                contrast=over(np.delete(norm, index, axis=0)), phase_contrast=over(np.delete(norm[index], top % 64)))
+
+
+def read_transformed_leak(decoder, frames, segment_of_frame, canvas_hw, candidates, geometries, key=0, L: int = 8, search_frames: int = 8) -> dict:
+    """A rotated (or rescaled) AND cropped leak's copy per segment: the translation is not known.  decoder: a DwtDctSvdDecoder
+    (blk 4; anything with its affine_phase_scores_u8 / decode_soft_affine_u8 -- a DctDecoder raises ValueError); frames: CUDA
+    uint8 [n, h, w, 3], the leak as it is; canvas_hw, candidates, key, L: as read_rescaled_leak; geometries: int64 [K, 6], the
+    LINEAR parts to try, each with the sub-pixel shifts to try (rotation_candidates(..., subpixel_shifts(2), subpixel_shifts(2))) --
+    whole-pixel translations need no entries.
+      1. the first ``search_frames`` frames are scored under every geometry and all 64 whole-pixel shifts of the canvas
+         (decoder.affine_phase_scores_u8) and best_shifted_geometry picks one shifted geometry;
+      2. all frames are read at it (decoder.decode_soft_affine_u8) and summed per segment;
+      3. shifts by whole units are left: they rotate the L positions by a constant, which align_segments resolves over all L bases.
+    -> dict(index, phase, geometry (the shifted one), normalised, contrast, phase_contrast, segments, soft_by_segment, base, picks,
+    score, runner_up_score, ambiguous).  No verdict on the contrasts."""
+    canvas_hw = (int(canvas_hw[0]), int(canvas_hw[1]))
+    geoms = _geometries(geometries)
+    if geoms.shape[0] < 1 or geoms.shape[1] != 6:
+        raise ValueError("geometries must hold at least one (ayy, ayx, by, axy, axx, bx)")
+    for need in ("affine_phase_scores_u8", "decode_soft_affine_u8"):
+        if not hasattr(decoder, need):
+            raise ValueError(f"{type(decoder).__name__} does not read at an affine geometry ({need}): only DwtDctSvd does")
+    scores, units = decoder.affine_phase_scores_u8(frames[:max(1, int(search_frames))], canvas_hw, geoms)
+    found = best_shifted_geometry(scores, units, geoms)
+    soft = decoder.decode_soft_affine_u8(frames, canvas_hw, found["geometry"], L)
+    out = _align_by_segment(soft, segment_of_frame, candidates, key)
+    out.update(found)
     return out
