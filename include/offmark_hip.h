@@ -642,6 +642,39 @@ int ofmk_svd_affine_phase_scores_rgb8(const uint8_t *in, int n, int h, int w, in
 int ofmk_svd_detect_soft_affine_rgb8(const uint8_t *in, int n, int h, int w, int H, int W, const ofmk_affine *geom, int L,
                                      const double *scales, int blk, long long *soft, void *stream, const ofmk_opts *opts);
 
+/* ---- reading a leak against its SOURCE frames: the sums of a registration step (BUILD EXTENSION) -------------------------------
+ * The operator who reads a leak holds the frames it was made from, so the leak's geometry can be fitted to them -- six parameters,
+ * Gauss-Newton on the luma difference, coarse to fine (offmark.resync.register_leak) -- and needs no list.  Interleaved u8 RGB; the
+ * codec takes no part.  Everything is an integer, so the device equals the NumPy statement (tests/_align.py) integer for integer.
+ *
+ *   Y = (R + 2*G + B + 2) >> 2, in 0..255.  T = Y of the source frame on the canvas H x W; Yw = Y of the bytes
+ *   ofmk_warp_affine_rgb8 gives for the leak frame under the geometry (ofmk_affine's rule, unchanged).
+ *       gy = T[y+1][x] - T[y-1][x]      gx = T[y][x+1] - T[y][x-1]                (twice the derivative)
+ *   Canvas pixel (y, x) CONTRIBUTES iff 1 <= y <= H-2, 1 <= x <= W-2 and it is inside the leak by ofmk_affine's rule.  With
+ *       yc = y - (H >> 1)    xc = x - (W >> 1)    sd = (gy*yc, gy*xc, gy, gx*yc, gx*xc, gx)    e = Yw - T
+ *   the 29 sums over the contributing pixels are
+ *       [0..20]  the upper triangle of sum sd sd^T, row-major (i <= j)      [21..26]  sum sd*e
+ *       [27]     sum e*e                                                     [28]      the number of contributing pixels
+ *   Overflow: H, W <= 4096 is required (else OFMK_E_ARG), so |sd| <= 255 * 2048 < 2^19, a product is below 2^38 and a frame has at
+ *   most 2^24 pixels: every sum of one frame stays below 2^62.  Sums of several frames are added by the caller (Python integers).
+ *
+ * ofmk_align_sums_rgb8: src is device u8 [n][H][W][3], src[f] the source of leak frame f; leak is device u8 [n][h][w][3]; cands is
+ *   DEVICE memory, ofmk_affine [K]; sums is device int64 [n][K][29], cleared by the call whatever it held.  A candidate out of
+ *   ofmk_affine's range leaves 29 zeros (the list is not read on the host).  A workgroup owns a tile of 64 x 64 canvas pixels of one
+ *   candidate and one frame and leaves at once when the tile lies wholly beyond one edge of the leak; the warped taps are formed as
+ *   in ofmk_svd_affine_scores_rgb8 and no warped frame is written; partial sums stay in registers, then wavefront, LDS and at most
+ *   29 64-bit atomics per workgroup -- integer adds, so the result does not depend on their order.  Candidates in gridDim.y and
+ *   frames in gridDim.z, chunked at 65535 and below 2^30 workgroups per launch.  Byte loads of src; no alignment is assumed.
+ *   Required, else OFMK_E_ARG: n >= 1, 8 <= H, W <= 4096, h, w >= 1 with h*w < 2^28, K >= 1, n*K < 2^40, no null pointer.
+ * ofmk_halve_rgb8: the pyramid's 2x2 box, out[Y][X][c] = (in[2Y][2X][c] + in[2Y][2X+1][c] + in[2Y+1][2X][c] + in[2Y+1][2X+1][c] + 2) >> 2,
+ *   device u8 [n][h/2][w/2][3], every byte written; an odd last row or column of the input is dropped.  Level l+1 pixel P sits at
+ *   level-l coordinate 2P + 1/2, for canvas and leak alike, so a geometry keeps its linear part between levels and its offsets
+ *   follow offmark.resync.level_down / level_up.  Required, else OFMK_E_ARG: n >= 1, h*w < 2^28, h/2 >= 8 and w/2 >= 8.
+ * Both calls allocate nothing, synchronise nothing and are graph capturable; both are timed as kind 4 (svd); the flags are ignored. */
+int ofmk_align_sums_rgb8(const uint8_t *src, const uint8_t *leak, int n, int h, int w, int H, int W, const ofmk_affine *cands, int K,
+                         long long *sums, void *stream, const ofmk_opts *opts);
+int ofmk_halve_rgb8(const uint8_t *in, int n, int h, int w, uint8_t *out, void *stream, const ofmk_opts *opts);
+
 /* ---- DeShuffler.degenerate's epilogue for a batch, on the device ---------------------------
  * src/offmark/degenerator/de_shuffler.py:17-22: mean of bits[i::L] (from `counts`), undo the key
  * permutation (`perm` = DeShuffler.payload_idx, device int32 [L]), threshold strictly above the

@@ -53,6 +53,7 @@
 #include "warp_kernels.hiph"
 #include "affine_kernels.hiph"
 #include "affine_phase_kernels.hiph"
+#include "align_kernels.hiph"
 
 namespace {
 
@@ -1980,6 +1981,65 @@ int ofmk_svd_detect_soft_affine_rgb8(const uint8_t *in, int n, int h, int w, int
         ac.frames = cf;
         ac.soft = soft + (size_t)f0 * L;
         OFMK_TIMED_LAUNCH(timing, svd_soft_affine_rgb8_kernel, xcd_grid(a.nunits, cf), dim3(kThreads), 0, cx.s, in + (size_t)f0 * a.frame_stride, ac);
+        return OFMK_OK;
+    });
+    HIP_TRY(hipGetLastError());
+    return OFMK_OK;
+}
+
+// ---- leaks read against their source frames (align_kernels.hiph; build extensions, not reference semantics) ----------------------
+// sums[f][k][0..28] = the Gauss-Newton sums of leak frame f warped by cands[k] (DEVICE memory, [K]) against source frame f; int64
+// [n][K][29], cleared here whatever it held; an out-of-range candidate leaves 29 zeros.  Chunks as ofmk_svd_affine_scores_rgb8.
+int ofmk_align_sums_rgb8(const uint8_t *src, const uint8_t *leak, int n, int h, int w, int H, int W, const ofmk_affine *cands, int K,
+                         long long *sums, void *stream, const ofmk_opts *opts) {
+    if (int orc = check_opts(opts)) return orc;
+    if (int rc = check_dims(n, H, W)) return rc;
+    if (H > kAlignMaxSide || W > kAlignMaxSide) return fail(OFMK_E_ARG, "canvas H, W must be at most 4096 (the sums are int64)%s");
+    if (int rc = check_leak_dims(h, w)) return rc;
+    if (!src || !leak || !cands || !sums) return fail(OFMK_E_ARG, "null pointer%s");
+    if (K < 1) return fail(OFMK_E_ARG, "K must be at least 1%s");
+    if ((long long)n * K >= (1LL << 40)) return fail(OFMK_E_ARG, "n * K must be < 2^40%s");
+    const Ctx cx = make_ctx(stream, opts);
+    HIP_TRY(launch_zero(sums, (size_t)n * K * kAlignSums * sizeof(long long), cx.s));
+    AlignArgs a;
+    a.h = h; a.w = w; a.H = H; a.W = W;
+    a.tiles_x = (W + kAlignTile - 1) / kAlignTile;
+    a.K = K;
+    a.leak_stride = (size_t)h * w * 3;
+    a.src_stride = (size_t)H * W * 3;
+    const long long tiles = (long long)a.tiles_x * ((H + kAlignTile - 1) / kAlignTile);
+    const AffineMap *dc = reinterpret_cast<const AffineMap *>(cands);
+    for_chunks(K, kMaxChunk, [&](int k0, int ck) {
+        const long long room = (1LL << 30) / (tiles * ck);                       // workgroups per launch stay below 2^30
+        const int cap = room < 1 ? 1 : room > kMaxChunk ? kMaxChunk : (int)room;
+        return for_chunks(n, cap, [&](int f0, int cf) {
+            ScopedTiming timing(KIND_SVD, cx);
+            OFMK_TIMED_LAUNCH(timing, align_sums_rgb8_kernel, dim3((unsigned)tiles, (unsigned)ck, (unsigned)cf), dim3(kThreads), 0, cx.s,
+                              src + (size_t)f0 * a.src_stride, leak + (size_t)f0 * a.leak_stride, dc + k0, a,
+                              reinterpret_cast<unsigned long long *>(sums) + ((size_t)f0 * K + k0) * kAlignSums);
+            return OFMK_OK;
+        });
+    });
+    HIP_TRY(hipGetLastError());
+    return OFMK_OK;
+}
+
+// The 2x2 box of the registration pyramid: u8 [n][h / 2][w / 2][3], every byte written; an odd last row or column is dropped.
+int ofmk_halve_rgb8(const uint8_t *in, int n, int h, int w, uint8_t *out, void *stream, const ofmk_opts *opts) {
+    if (int orc = check_opts(opts)) return orc;
+    if (n <= 0) return fail(OFMK_E_ARG, "n must be positive%s");
+    if (!in || !out) return fail(OFMK_E_ARG, "null pointer%s");
+    if (int rc = check_leak_dims(h, w)) return rc;
+    if (h / 2 < 8 || w / 2 < 8) return fail(OFMK_E_ARG, "both halved sides must be at least 8%s");
+    const Ctx cx = make_ctx(stream, opts);
+    HalveArgs a;
+    a.w = w; a.Ho = h / 2; a.Wo = w / 2;
+    a.in_stride = (size_t)h * w * 3;
+    a.out_stride = (size_t)a.Ho * a.Wo * 3;
+    for_chunks(n, kMaxChunk, [&](int f0, int cf) {
+        ScopedTiming timing(KIND_SVD, cx);
+        OFMK_TIMED_LAUNCH(timing, halve_rgb8_kernel, grid_2d(a.Ho * a.Wo, cf), dim3(kThreads), 0, cx.s, in + (size_t)f0 * a.in_stride,
+                          out + (size_t)f0 * a.out_stride, a);
         return OFMK_OK;
     });
     HIP_TRY(hipGetLastError());

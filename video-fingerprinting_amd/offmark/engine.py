@@ -758,6 +758,37 @@ class DctEngine:
                                                              _hip.current_stream(), self._o()))
         return soft
 
+    # -- leaks read against their source frames: the sums of a registration step (build extension; offmark.resync.register_leak) --
+    def align_sums(self, sources, frames, cands, sums=None):
+        """The 29 Gauss-Newton sums of every leak frame warped by every candidate against its source frame (include/offmark_hip.h:
+        ofmk_align_sums_rgb8).  sources: uint8 [n, H, W, 3], H, W <= 4096; frames: uint8 [n, h, w, 3]; ``cands``: int64 [K, 6], a
+        tensor on this device or an array (copied there) -> int64 [n, K, 29]; a candidate out of range has 29 zeros.  No warped
+        frame is written."""
+        t = self.torch
+        n, H, W = self._check_frames(sources, t.uint8)
+        m, h, w = self._check_frames(frames, t.uint8)
+        if m != n:
+            raise ValueError("one source frame per leak frame")
+        if not isinstance(cands, t.Tensor):
+            cands = t.from_numpy(np.ascontiguousarray(np.asarray(cands, dtype=np.int64)))
+        cands = cands.to(device=self.device, dtype=t.int64).contiguous()
+        if cands.dim() != 2 or cands.shape[1] != 6 or cands.shape[0] < 1:
+            raise ValueError("cands must be int64 [K, 6] with K >= 1")
+        K = int(cands.shape[0])
+        sums = self._soft(sums, K, 29, copies=n)
+        _hip.check(self.lib.ofmk_align_sums_rgb8(sources.data_ptr(), frames.data_ptr(), n, h, w, H, W, cands.data_ptr(), K, sums.data_ptr(),
+                                                 _hip.current_stream(), self._o()))
+        return sums
+
+    def halve(self, frames, out=None):
+        """The 2x2 box of the registration pyramid: uint8 [n, h, w, 3] -> uint8 [n, h // 2, w // 2, 3], (a + b + c + d + 2) >> 2 per
+        channel; an odd last row or column is dropped; both halved sides must be at least 8."""
+        t = self.torch
+        n, h, w = self._check_frames(frames, t.uint8)
+        out = self._out(out, frames, (n, h // 2, w // 2, 3))
+        _hip.check(self.lib.ofmk_halve_rgb8(frames.data_ptr(), n, h, w, out.data_ptr(), _hip.current_stream(), self._o()))
+        return out
+
     def svd_embed_detect(self, frames, wm, L, scale=15, wm_row=None, out=None, want_bits=False, scales=None, blk=4, counts=None,
                          partial=False):
         t = self.torch

@@ -86,6 +86,18 @@ class DwtDctSvdDecoder:
         """decode_soft_warp_u8 at an affine ``geom`` of six (engine.svd_detect_soft_affine)."""
         return self.engine.svd_detect_soft_affine(frames, canvas_hw, geom, L, scales=self._scales, blk=self.blk)
 
+    # -- leaks read against their source frames (build extension: offmark.resync.register_leak / read_registered_leak) ------------
+    def align_sums_u8(self, sources, frames, canvas_hw, cands):
+        """sources: CUDA uint8 [n, H, W, 3] with (H, W) = canvas_hw, frames: CUDA uint8 [n, h, w, 3], cands: int64 [K, 6] -> int64
+        [n, K, 29] on device: the sums of one registration step (engine.align_sums)."""
+        if tuple(int(v) for v in sources.shape[1:3]) != (int(canvas_hw[0]), int(canvas_hw[1])):
+            raise ValueError("the source frames must have the canvas's size")
+        return self.engine.align_sums(sources, frames, cands)
+
+    def halve_u8(self, frames):
+        """frames: CUDA uint8 [n, h, w, 3] -> CUDA uint8 [n, h // 2, w // 2, 3], the 2x2 box (engine.halve)."""
+        return self.engine.halve(frames)
+
     def sync_scores_planes_yuv420(self, planes, height, width, layout="i420"):
         """planes: CUDA uint8 [n, 1.5*H*W] (I420 or NV12), even H, W >= 8 -> int64 [n, 64] on device: sync_scores_u8's sums at the
         phases with even py and px, 0 elsewhere -- an odd crop offset does not exist on 4:2:0 planes (engine.svd_sync_scores_yuv420)."""

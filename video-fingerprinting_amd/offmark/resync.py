@@ -64,8 +64,17 @@ the 72x104 recipe rotated by 2 degrees and cropped, first 4 frames):
     about its centre (the translation is then within about 0.1 px of a multiple of half a pixel); it is NOT a cover of an
     arbitrary translation, which takes subpixel_shifts(8).
 The contrasts are thin (about 1.05 between candidates, 1.07-1.09 between phases on 4 small frames): no verdict is given.
-4:2:0 planes under any resampling, blk 8, perspective, the DCT codec under an affine map and a search of the linear part itself
-(anything beyond scoring a given list of linear parts and sub-pixel shifts) are not handled.
+WITH THE SOURCE FRAMES AT HAND -- the operator who reads a leak marked the video -- nothing has to be listed: ``register_leak`` fits
+the leak's geometry to its source, six parameters by Gauss-Newton on the luma difference between the warped leak and the source,
+coarse to fine over a pyramid of 2x2 halvings (``level_down`` / ``level_up`` carry a geometry between levels), each step
+(``align_step``) from 29 integer sums per frame that ``DwtDctSvdDecoder.align_sums_u8`` computes in one fused call without writing a
+warped frame.  The result lies on the source's own pixel grid, so ``read_registered_leak`` reads with base 0 and no search.  On the
+NumPy statement (tests/_align.py, the leaks above, first 4 frames, from the centred UNROTATED start) the registered geometry lies
+0.10 / 0.08 px at the canvas corners from the listed truth of the two leaks and reads a stronger mark than it (sum |m| per unit
+12.9 k / 12.6 k against 12.1 k / 12.2 k; 10.0 k / 10.2 k for the unmarked sources registered the same way); a leak rotated by -3
+degrees with step 1.10 registers from scale 1 to 0.016 px; starts shifted by (12, 10) and (-16, 14) px need one halving.
+4:2:0 planes under any resampling, blk 8, perspective, the DCT codec under an affine map and, without the source frames, a search
+of the linear part itself (anything beyond scoring a given list of linear parts and sub-pixel shifts) are not handled.
 """
 from __future__ import annotations
 
@@ -484,4 +493,185 @@ def read_transformed_leak(decoder, frames, segment_of_frame, canvas_hw, candidat
     soft = decoder.decode_soft_affine_u8(frames, canvas_hw, found["geometry"], L)
     out = _align_by_segment(soft, segment_of_frame, candidates, key)
     out.update(found)
+    return out
+
+
+# ---- leaks read against their SOURCE frames: registration in place of a geometry list ------------------------------------------------
+ALIGN_SUMS = 29               # per frame and candidate: 21 of sum sd sd^T (upper triangle, row-major), 6 of sum sd e, sum e^2, the count
+ALIGN_MIN_PIXELS = 384        # fewer contributing pixels than this give no step
+ALIGN_MAX_SIDE = 4096         # canvas H, W: keeps a frame's sums inside int64
+
+
+class NoAlignStep(ValueError):
+    """align_step has no step to give; the message says why."""
+
+
+def level_down(geom) -> tuple:
+    """The geometry one pyramid level up (both the canvas and the leak halved by the 2x2 box, odd last row / column dropped): level
+    l + 1 pixel P sits at level-l coordinate 2 P + 1/2, so the linear part stays and by' = (by + (ayy + ayx) / 2 - 2^15) / 2, bx alike,
+    each rounded once to Q16 (exact integers, halves up)."""
+    ayy, ayx, by, axy, axx, bx = (int(v) for v in np.asarray(_host(geom)).reshape(-1))
+    return ayy, ayx, _round_div(2 * by + ayy + ayx - WARP_ONE, 4), axy, axx, _round_div(2 * bx + axy + axx - WARP_ONE, 4)
+
+
+def level_up(geom) -> tuple:
+    """level_down's inverse: by' = 2 by + 2^15 - (ayy + ayx) / 2, bx alike, each rounded once to Q16.  level_up(level_down(g)) moves no
+    sample by more than 2^-16 px per axis (a half down, doubled; when ayy + ayx is odd a quarter down and a half up)."""
+    ayy, ayx, by, axy, axx, bx = (int(v) for v in np.asarray(_host(geom)).reshape(-1))
+    return ayy, ayx, _round_div(4 * by + WARP_ONE - ayy - ayx, 2), axy, axx, _round_div(4 * bx + WARP_ONE - axy - axx, 2)
+
+
+def corner_move(g0, g1, canvas_hw) -> float:
+    """The largest distance, in leak pixels, between the samples of the four canvas corner pixels under g0 and under g1."""
+    a, b = [int(v) for v in g0], [int(v) for v in g1]
+    worst = 0.0
+    for y in (0, int(canvas_hw[0]) - 1):
+        for x in (0, int(canvas_hw[1]) - 1):
+            dy = (b[0] - a[0]) * y + (b[1] - a[1]) * x + b[2] - a[2]
+            dx = (b[3] - a[3]) * y + (b[4] - a[4]) * x + b[5] - a[5]
+            worst = max(worst, float(np.hypot(dy, dx)) / WARP_ONE)
+    return worst
+
+
+def _total_sums(sums) -> list:
+    """[..., 29] sums -> 29 Python integers: the frames' sums added without a width."""
+    s = np.asarray(_host(sums), dtype=np.int64).reshape(-1, ALIGN_SUMS)
+    return [sum(int(v) for v in s[:, i]) for i in range(ALIGN_SUMS)]
+
+
+def align_step(geom, sums, canvas_hw) -> tuple:
+    """One Gauss-Newton step of the leak's geometry towards its source.  sums: int64 [..., 29] of decoder.align_sums_u8 under
+    ``geom`` (include/offmark_hip.h: ofmk_align_sums_rgb8), any number of frames; they are added as Python integers.  With Hm the
+    6x6 matrix and b the 6-vector of the sums (gradients are TWICE the derivative), d = solve(Hm / 4, b / 2) in float64,
+    M = [[d0, d1], [d3, d4]], t = (d2, d5), c = (H >> 1, W >> 1): the warped leak at canvas pixel p looks like the source at
+    A(p) = p + M (p - c) + t, so the step is g' = g o A^-1, each coefficient rounded once to Q16.  Raises NoAlignStep when fewer than
+    384 pixels contribute or Hm is not positive definite (a flat source: its Cholesky factorisation fails)."""
+    g = [int(v) for v in np.asarray(_host(geom)).reshape(-1)]
+    if len(g) != 6:
+        raise ValueError("an affine geometry is (ayy, ayx, by, axy, axx, bx)")
+    tot = _total_sums(sums)
+    if tot[28] < ALIGN_MIN_PIXELS:
+        raise NoAlignStep(f"{tot[28]} contributing pixels, fewer than {ALIGN_MIN_PIXELS}")
+    Hm = np.zeros((6, 6), np.float64)
+    k = 0
+    for i in range(6):
+        for j in range(i, 6):
+            Hm[i, j] = Hm[j, i] = float(tot[k]) / 4.0
+            k += 1
+    b = np.array([float(v) / 2.0 for v in tot[21:27]], np.float64)
+    try:
+        np.linalg.cholesky(Hm)
+    except np.linalg.LinAlgError:
+        raise NoAlignStep("the normal matrix is not positive definite (a source without gradients)") from None
+    d = np.linalg.solve(Hm, b)
+    M = np.array([[d[0], d[1]], [d[3], d[4]]])
+    t = np.array([d[2], d[5]])
+    c = np.array([float(int(canvas_hw[0]) >> 1), float(int(canvas_hw[1]) >> 1)])
+    try:
+        inv = np.linalg.inv(np.eye(2) + M)
+    except np.linalg.LinAlgError:
+        raise NoAlignStep("the step is singular") from None
+    lin = np.array([[g[0], g[1]], [g[3], g[4]]], np.float64) @ inv           # g o A^-1: q -> L inv q + L inv (M c - t) + b
+    off = lin @ (M @ c - t) + np.array([g[2], g[5]], np.float64)
+    vals = (lin[0, 0], lin[0, 1], off[0], lin[1, 0], lin[1, 1], off[1])
+    if not all(np.isfinite(v) and abs(v) < 2.0 ** 62 for v in vals):
+        raise NoAlignStep("the step is not finite")
+    return tuple(int(np.rint(v)) for v in vals)
+
+
+def default_levels(leak_hw) -> int:
+    """Pyramid levels of register_leak, the full resolution included: the leak is halved while its shorter side stays >= 48."""
+    side, levels = min(int(leak_hw[0]), int(leak_hw[1])), 1
+    while side // 2 >= 48:
+        side //= 2
+        levels += 1
+    return levels
+
+
+def register_leak(decoder, sources, frames, canvas_hw, start=None, levels=None, max_iters: int = 15, tol_px: float = 1.0 / 64) -> dict:
+    """The geometry of a leak from its SOURCE frames, with no list: Gauss-Newton on the luma difference between the warped leak and
+    the source, six parameters, coarse to fine.  decoder: a DwtDctSvdDecoder (anything with its align_sums_u8 / halve_u8);
+    sources: uint8 [n, H, W, 3], frame i's source on the canvas; frames: uint8 [n, h, w, 3], the leak; start: the first geometry
+    (default affine_of_rotation(canvas_hw, leak_hw, 0.0): centred, unrotated); levels: pyramid levels, full resolution included
+    (default_levels).  Each level iterates align_step until the four canvas corners move less than ``tol_px`` leak pixels or
+    ``max_iters`` steps are taken -- the integer iteration wobbles in its last Q16 bits and has no exact fixed point --, then hands
+    level_up of its geometry to the finer level.  -> dict(geometry, iterations (per level, coarse to fine), rms (the luma residual at
+    the last geometry that was measured, full resolution), pixels (that measurement's contributing pixels, all frames), units
+    (counting units of the geometry), converged (the finest level met ``tol_px``), reason (None, or why not)).  Nothing is raised for a
+    leak that cannot be registered: ``converged`` is False and ``reason`` says why."""
+    canvas_hw = (int(canvas_hw[0]), int(canvas_hw[1]))
+    leak_hw = (int(frames.shape[1]), int(frames.shape[2]))
+    if tuple(int(v) for v in sources.shape[:3]) != (int(frames.shape[0]), *canvas_hw):
+        raise ValueError("sources must be [n, H, W, 3] with one canvas-sized frame per leak frame")
+    g = tuple(int(v) for v in (affine_of_rotation(canvas_hw, leak_hw, 0.0) if start is None else np.asarray(_host(start)).reshape(-1)))
+    if len(g) != 6:
+        raise ValueError("start must be an affine geometry of six")
+    levels = default_levels(leak_hw) if levels is None else int(levels)
+    if levels < 1:
+        raise ValueError("levels must be at least 1")
+    pyramid = [(sources, frames)]
+    for _ in range(levels - 1):
+        s, f = pyramid[-1]
+        pyramid.append((decoder.halve_u8(s), decoder.halve_u8(f)))
+        g = level_down(g)
+    iterations, reason, met, rms, pixels = [], None, False, None, 0
+    for level in range(levels - 1, -1, -1):
+        s, f = pyramid[level]
+        hw = (int(s.shape[1]), int(s.shape[2]))
+        steps, met = 0, False
+        while steps < int(max_iters) and reason is None and not met:
+            tot = _total_sums(decoder.align_sums_u8(s, f, hw, np.asarray([g], dtype=np.int64)))
+            if level == 0:
+                pixels = tot[28]
+                rms = float(np.sqrt(tot[27] / tot[28])) if tot[28] else None
+            try:
+                nxt = align_step(g, tot, hw)
+                if not _affine_ok(nxt):
+                    raise NoAlignStep("the step leaves the affine warp's range")
+            except NoAlignStep as exc:
+                reason = f"level {level}: {exc}"
+                break
+            steps += 1
+            met = corner_move(g, nxt, hw) < float(tol_px)
+            g = nxt
+        iterations.append(steps)
+        if reason is not None:
+            iterations += [0] * level
+            for _ in range(level):
+                g = level_up(g)
+            break
+        if level:
+            g = level_up(g)
+    if reason is None and not met:
+        reason = f"level 0: the corners still move by {tol_px} px or more after {max_iters} steps"
+    units = int(affine_units(leak_hw, canvas_hw, g).sum()) if _affine_ok(g) else 0
+    return dict(geometry=g, iterations=iterations, rms=rms, pixels=pixels, units=units, converged=reason is None, reason=reason)
+
+
+def read_registered_leak(decoder, frames, sources, segment_of_frame, canvas_hw, candidates, key=0, L: int = 8, search_frames: int = 8,
+                         **register) -> dict:
+    """A transformed leak's copy per segment, read against its SOURCE frames: no list of geometries.  decoder: a DwtDctSvdDecoder
+    (blk 4; anything with its align_sums_u8 / halve_u8 / decode_soft_affine_u8 -- a DctDecoder raises ValueError); frames: uint8
+    [n, h, w, 3], the leak; sources: uint8 [n, H, W, 3], sources[i] is frame i's unmarked (or marked) source; the other arguments as
+    read_transformed_leak; ``register``: start, levels, max_iters, tol_px of register_leak.
+      1. register_leak on the first ``search_frames`` frames and their sources;
+      2. all frames are read at that geometry (decoder.decode_soft_affine_u8) and summed per segment;
+      3. the geometry lies on the source's own pixel grid, so no rotation of the positions is left: align_segments with bases (0,).
+    -> read_transformed_leak's keys (index 0, phase (0, 0), base 0, runner_up_score None; normalised = the geometry's score /
+    (2^14 * units * frames) on the search frames where the decoder has affine_scores_u8, else None; contrast and phase_contrast
+    None: nothing was ranked) plus ``registration``, register_leak's report.  No verdict: judge ``registration['converged']``."""
+    canvas_hw = (int(canvas_hw[0]), int(canvas_hw[1]))
+    for need in ("align_sums_u8", "halve_u8", "decode_soft_affine_u8"):
+        if not hasattr(decoder, need):
+            raise ValueError(f"{type(decoder).__name__} does not read at an affine geometry ({need}): only DwtDctSvd does")
+    k = max(1, int(search_frames))
+    report = register_leak(decoder, sources[:k], frames[:k], canvas_hw, **register)
+    geom = report["geometry"]
+    normalised = None
+    if hasattr(decoder, "affine_scores_u8") and report["units"] > 0:
+        s = _host(decoder.affine_scores_u8(frames[:k], canvas_hw, np.asarray([geom], dtype=np.int64))).astype(np.int64)
+        normalised = float(s.sum()) / (float(ONE) * report["units"] * s.shape[0])
+    soft = decoder.decode_soft_affine_u8(frames, canvas_hw, geom, L)
+    out = _align_by_segment(soft, segment_of_frame, candidates, key, bases=(0,))
+    out.update(index=0, phase=(0, 0), geometry=geom, normalised=normalised, contrast=None, phase_contrast=None, registration=report)
     return out
