@@ -675,6 +675,38 @@ int ofmk_align_sums_rgb8(const uint8_t *src, const uint8_t *leak, int n, int h, 
                          long long *sums, void *stream, const ofmk_opts *opts);
 int ofmk_halve_rgb8(const uint8_t *in, int n, int h, int w, uint8_t *out, void *stream, const ofmk_opts *opts);
 
+/* ---- matching the frames of a leaked CLIP to the frames of its source video (BUILD EXTENSION) ---------------------------------
+ * A leak is a clip: it starts somewhere in the video, and a frame-rate conversion has dropped or doubled frames.  Which source frame
+ * a leak frame came from is found in two passes (offmark.temporal): a coarse one on 8 x 8 luma thumbnails, and an exact one on the
+ * luma residual at the registered geometry.  Interleaved u8 RGB; the codec takes no part.  Everything is an integer, so the device
+ * equals the NumPy statement (tests/_temporal.py) byte for byte.  Y = (R + 2*G + B + 2) >> 2 as above.
+ *
+ * ofmk_signature_rgb8: in is device u8 [n][h][w][3]; sig is device u8 [n][64], every byte written.  Cell (i, j), 0 <= i, j < 8,
+ *   covers rows (i*h) >> 3 .. ((i+1)*h) >> 3 - 1 and columns (j*w) >> 3 .. ((j+1)*w) >> 3 - 1; with A its area,
+ *       sig[f][8*i + j] = (2 * sum Y + A) / (2 * A)                                 (the rounded mean, halves up, 0..255)
+ *   A workgroup per frame and row of cells, frames in gridDim.x (no chunking).  No alignment is assumed: four pixels are fetched as
+ *   three dwords at any address, the columns past the last group of four with byte loads; no load leaves the frame.
+ *   Required, else OFMK_E_ARG: n >= 1, h, w >= 8, h*w < 2^28, no null pointer.
+ * ofmk_signature_distances: a is device u8 [m][64], b device u8 [N][64]; dist is device int32 [m][N], every entry written:
+ *       dist[i][t] = sum over c < 64 of |a[i][c] - b[t][c]|                         (at most 16320)
+ *   A thread keeps one row of b in 16 registers, 32 rows of a sit in LDS, four bytes per v_sad_u8, stores coalesced along N.
+ *   Required, else OFMK_E_ARG: m, N >= 1, m*N < 2^40, no null pointer.
+ * ofmk_align_residuals_rgb8: lib is device u8 [N][H][W][3], the source frames; leak is device u8 [m][h][w][3]; first is DEVICE int32
+ *   [m]; geom is ONE geometry in HOST memory (ofmk_affine's rules, else OFMK_E_ARG); res is device int64 [m][span][2], cleared by the
+ *   call whatever it held.  With s = first[i] + j, res[i][j] = (sum e*e, the number of contributing pixels): entries [27] and [28] of
+ *   ofmk_align_sums_rgb8 for source lib[s] and leak frame i under geom -- the same contributing-pixel rule, the same warp.  s
+ *   outside 0..N-1 leaves (0, 0); the list is not read on the host.  A workgroup owns a tile of 64 x 64 canvas pixels of one leak
+ *   frame: it forms the warped luma of its pixels once, then walks the span sources reading only their luma; each source's squares
+ *   are reduced in 32 bits (a tile's stay below 2^29), then at most 2*span 64-bit atomics per workgroup -- integer adds, so the order
+ *   is free.  No warped frame and no gathered source is written.  Leak frames in gridDim.y, chunked at 65535.
+ *   Required, else OFMK_E_ARG: m, N >= 1, 1 <= span <= 16, 8 <= H, W <= 4096, h, w >= 1 with h*w < 2^28, no null pointer.
+ * The three calls allocate nothing, synchronise nothing and are graph capturable; all are timed as kind 4 (svd); the flags are
+ * ignored. */
+int ofmk_signature_rgb8(const uint8_t *in, int n, int h, int w, uint8_t *sig, void *stream, const ofmk_opts *opts);
+int ofmk_signature_distances(const uint8_t *a, int m, const uint8_t *b, int N, int32_t *dist, void *stream, const ofmk_opts *opts);
+int ofmk_align_residuals_rgb8(const uint8_t *lib, int N, const uint8_t *leak, int m, int h, int w, int H, int W, const int32_t *first,
+                              int span, const ofmk_affine *geom, long long *res, void *stream, const ofmk_opts *opts);
+
 /* ---- DeShuffler.degenerate's epilogue for a batch, on the device ---------------------------
  * src/offmark/degenerator/de_shuffler.py:17-22: mean of bits[i::L] (from `counts`), undo the key
  * permutation (`perm` = DeShuffler.payload_idx, device int32 [L]), threshold strictly above the

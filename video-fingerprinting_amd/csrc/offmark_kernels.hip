@@ -54,6 +54,7 @@
 #include "affine_kernels.hiph"
 #include "affine_phase_kernels.hiph"
 #include "align_kernels.hiph"
+#include "temporal_kernels.hiph"
 
 namespace {
 
@@ -2040,6 +2041,69 @@ int ofmk_halve_rgb8(const uint8_t *in, int n, int h, int w, uint8_t *out, void *
         ScopedTiming timing(KIND_SVD, cx);
         OFMK_TIMED_LAUNCH(timing, halve_rgb8_kernel, grid_2d(a.Ho * a.Wo, cf), dim3(kThreads), 0, cx.s, in + (size_t)f0 * a.in_stride,
                           out + (size_t)f0 * a.out_stride, a);
+        return OFMK_OK;
+    });
+    HIP_TRY(hipGetLastError());
+    return OFMK_OK;
+}
+
+// ---- matching a leaked clip's frames to the source video's (temporal_kernels.hiph; build extensions, not reference semantics) -----
+// sig[f][8 i + j] = the rounded mean luma of cell (i, j) of frame f; u8 [n][64], every byte written.  Frames in gridDim.x: no chunks.
+int ofmk_signature_rgb8(const uint8_t *in, int n, int h, int w, uint8_t *sig, void *stream, const ofmk_opts *opts) {
+    if (int orc = check_opts(opts)) return orc;
+    if (int rc = check_dims(n, h, w)) return rc;
+    if (!in || !sig) return fail(OFMK_E_ARG, "null pointer%s");
+    const Ctx cx = make_ctx(stream, opts);
+    SignatureArgs a;
+    a.h = h; a.w = w;
+    a.frame_stride = (size_t)h * w * 3;
+    ScopedTiming timing(KIND_SVD, cx);
+    OFMK_TIMED_LAUNCH(timing, signature_rgb8_kernel, dim3((unsigned)n, 8u), dim3(kThreads), 0, cx.s, in, sig, a);
+    HIP_TRY(hipGetLastError());
+    return OFMK_OK;
+}
+
+// dist[i][t] = sum over the 64 bytes of |a[i][c] - b[t][c]|; int32 [m][N], every entry written.
+int ofmk_signature_distances(const uint8_t *a, int m, const uint8_t *b, int N, int32_t *dist, void *stream, const ofmk_opts *opts) {
+    if (int orc = check_opts(opts)) return orc;
+    if (m < 1 || N < 1) return fail(OFMK_E_ARG, "m and N must be at least 1%s");
+    if ((long long)m * N >= (1LL << 40)) return fail(OFMK_E_ARG, "m * N must be < 2^40%s");
+    if (!a || !b || !dist) return fail(OFMK_E_ARG, "null pointer%s");
+    const Ctx cx = make_ctx(stream, opts);
+    const int tiles = (m + kDistRows - 1) / kDistRows;
+    ScopedTiming timing(KIND_SVD, cx);
+    OFMK_TIMED_LAUNCH(timing, signature_distances_kernel, dim3((unsigned)((N + kThreads - 1) / kThreads), (unsigned)(tiles < kMaxChunk ? tiles : kMaxChunk)),
+                      dim3(kThreads), 0, cx.s, a, m, b, N, dist);
+    HIP_TRY(hipGetLastError());
+    return OFMK_OK;
+}
+
+// res[i][j] = (sum e^2, contributing pixels) of leak frame i warped by *geom (HOST memory) against source lib[first[i] + j], j < span:
+// ofmk_align_sums_rgb8's sums [27] and [28] of that pair; int64 [m][span][2], cleared here whatever it held.  first: DEVICE int32 [m];
+// a source index outside 0..N-1 leaves (0, 0).
+int ofmk_align_residuals_rgb8(const uint8_t *lib, int N, const uint8_t *leak, int m, int h, int w, int H, int W, const int32_t *first, int span,
+                              const ofmk_affine *geom, long long *res, void *stream, const ofmk_opts *opts) {
+    if (int orc = check_opts(opts)) return orc;
+    if (int rc = check_dims(m, H, W)) return rc;
+    if (N < 1) return fail(OFMK_E_ARG, "N must be at least 1%s");
+    if (H > kAlignMaxSide || W > kAlignMaxSide) return fail(OFMK_E_ARG, "canvas H, W must be at most 4096%s");
+    if (int rc = check_leak_dims(h, w)) return rc;
+    if (span < 1 || span > kResidualMaxSpan) return fail(OFMK_E_ARG, "span must be in [1, 16]%s");
+    if (!lib || !leak || !first || !geom || !res) return fail(OFMK_E_ARG, "null pointer%s");
+    ResidualArgs a;
+    if (int rc = check_affine_map(geom, a.m)) return rc;
+    const Ctx cx = make_ctx(stream, opts);
+    HIP_TRY(launch_zero(res, (size_t)m * span * 2 * sizeof(long long), cx.s));
+    a.h = h; a.w = w; a.H = H; a.W = W;
+    a.tiles_x = (W + kAlignTile - 1) / kAlignTile;
+    a.N = N; a.span = span;
+    a.leak_stride = (size_t)h * w * 3;
+    a.src_stride = (size_t)H * W * 3;
+    const int tiles = a.tiles_x * ((H + kAlignTile - 1) / kAlignTile);          // at most 64 * 64
+    for_chunks(m, kMaxChunk, [&](int f0, int cf) {
+        ScopedTiming timing(KIND_SVD, cx);
+        OFMK_TIMED_LAUNCH(timing, align_residuals_rgb8_kernel, dim3((unsigned)tiles, (unsigned)cf), dim3(kThreads), 0, cx.s, lib,
+                          leak + (size_t)f0 * a.leak_stride, first + f0, a, reinterpret_cast<unsigned long long *>(res) + (size_t)f0 * span * 2);
         return OFMK_OK;
     });
     HIP_TRY(hipGetLastError());

@@ -129,6 +129,9 @@ SIGNATURES = {
     "ofmk_svd_detect_soft_affine_rgb8": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _ap, _i32, _dp, _i32, _vp, _vp, _op]),
     "ofmk_align_sums_rgb8": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _op]),
     "ofmk_halve_rgb8": (_i32, [_vp, _i32, _i32, _i32, _vp, _vp, _op]),
+    "ofmk_signature_rgb8": (_i32, [_vp, _i32, _i32, _i32, _vp, _vp, _op]),
+    "ofmk_signature_distances": (_i32, [_vp, _i32, _vp, _i32, _vp, _vp, _op]),
+    "ofmk_align_residuals_rgb8": (_i32, [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _ap, _vp, _vp, _op]),
     "ofmk_probe_xcc": (_i32, [_vp, _i32, _vp, _op]),
     "ofmk_hbm_copy": (_i32, [_vp, _vp, _sz, _vp]),
     "ofmk_hbm_read": (_i32, [_vp, _sz, _vp, _vp]),

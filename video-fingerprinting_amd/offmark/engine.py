@@ -789,6 +789,55 @@ class DctEngine:
         _hip.check(self.lib.ofmk_halve_rgb8(frames.data_ptr(), n, h, w, out.data_ptr(), _hip.current_stream(), self._o()))
         return out
 
+    # -- a leaked clip's frames matched to the source video's (build extension; offmark.temporal) -------------------------------------
+    def signatures(self, frames, out=None):
+        """The 8 x 8 luma thumbnail of every frame: uint8 [n, h, w, 3], h, w >= 8 -> uint8 [n, 64], cell (i, j) at 8 * i + j, the
+        rounded mean of Y = (R + 2 G + B + 2) >> 2 over rows (i h) >> 3 .. ((i + 1) h) >> 3 - 1 and columns likewise
+        (include/offmark_hip.h: ofmk_signature_rgb8)."""
+        t = self.torch
+        n, h, w = self._check_frames(frames, t.uint8)
+        out = self._buffer("out", out, (n, 64), t.uint8, self.device)
+        _hip.check(self.lib.ofmk_signature_rgb8(frames.data_ptr(), n, h, w, out.data_ptr(), _hip.current_stream(), self._o()))
+        return out
+
+    def _signature_list(self, name, s):
+        t = self.torch
+        if not (isinstance(s, t.Tensor) and s.is_cuda and s.dtype == t.uint8 and s.dim() == 2 and s.shape[1] == 64 and s.shape[0] >= 1
+                and s.is_contiguous()):
+            raise ValueError(f"{name} must be a contiguous CUDA uint8 tensor [k, 64] with k >= 1")
+        return int(s.shape[0])
+
+    def signature_distances(self, a, b, out=None):
+        """The L1 distances between two signature lists: uint8 [m, 64] and uint8 [N, 64] -> int32 [m, N], at most 16320
+        (ofmk_signature_distances)."""
+        m, N = self._signature_list("a", a), self._signature_list("b", b)
+        out = self._buffer("out", out, (m, N), self.torch.int32, self.device)
+        _hip.check(self.lib.ofmk_signature_distances(a.data_ptr(), m, b.data_ptr(), N, out.data_ptr(), _hip.current_stream(), self._o()))
+        return out
+
+    def align_residuals(self, library, frames, first, span, geom, out=None):
+        """The luma residual of every leak frame against a window of source frames under ONE geometry: library uint8 [N, H, W, 3],
+        H, W <= 4096; frames uint8 [m, h, w, 3]; ``first``: int32 [m], a tensor on this device or an array (copied there); span in
+        1..16 -> int64 [m, span, 2]: entry j of frame i is (sum e^2, contributing pixels) against library[first[i] + j], exactly
+        align_sums' [27] and [28] of that pair; (0, 0) where the index leaves the library (ofmk_align_residuals_rgb8).  No warped frame
+        and no gathered source is written."""
+        t = self.torch
+        N, H, W = self._check_frames(library, t.uint8)
+        m, h, w = self._check_frames(frames, t.uint8)
+        if not isinstance(first, t.Tensor):
+            first = t.from_numpy(np.ascontiguousarray(np.asarray(first, dtype=np.int32)))
+        first = first.to(device=self.device, dtype=t.int32).contiguous()
+        if first.dim() != 1 or first.shape[0] != m:
+            raise ValueError("first must be int32 [m], one entry per leak frame")
+        span = int(span)
+        if not 1 <= span <= 16:
+            raise ValueError("span must be in 1..16")
+        out = self._soft(out, span, 2, copies=m)
+        g = self._affine_geom(geom)
+        _hip.check(self.lib.ofmk_align_residuals_rgb8(library.data_ptr(), N, frames.data_ptr(), m, h, w, H, W, first.data_ptr(), span, C.byref(g),
+                                                      out.data_ptr(), _hip.current_stream(), self._o()))
+        return out
+
     def svd_embed_detect(self, frames, wm, L, scale=15, wm_row=None, out=None, want_bits=False, scales=None, blk=4, counts=None,
                          partial=False):
         t = self.torch

@@ -98,6 +98,23 @@ class DwtDctSvdDecoder:
         """frames: CUDA uint8 [n, h, w, 3] -> CUDA uint8 [n, h // 2, w // 2, 3], the 2x2 box (engine.halve)."""
         return self.engine.halve(frames)
 
+    # -- a leaked clip's frames matched to the source video's (build extension: offmark.temporal.read_leak_clip) ------------------------
+    def signatures_u8(self, frames):
+        """frames: CUDA uint8 [n, h, w, 3] -> CUDA uint8 [n, 64], the 8 x 8 luma thumbnails (engine.signatures)."""
+        return self.engine.signatures(frames)
+
+    def signature_distances_u8(self, a, b):
+        """a: CUDA uint8 [m, 64], b: CUDA uint8 [N, 64] -> int32 [m, N] on device, the L1 distances (engine.signature_distances)."""
+        return self.engine.signature_distances(a, b)
+
+    def align_residuals_u8(self, library, frames, canvas_hw, first, span, geom):
+        """library: CUDA uint8 [N, H, W, 3] with (H, W) = canvas_hw, frames: CUDA uint8 [m, h, w, 3], first: int32 [m] -> int64
+        [m, span, 2] on device: (sum e^2, contributing pixels) of frame i against library[first[i] + j] under ``geom``
+        (engine.align_residuals)."""
+        if tuple(int(v) for v in library.shape[1:3]) != (int(canvas_hw[0]), int(canvas_hw[1])):
+            raise ValueError("the library frames must have the canvas's size")
+        return self.engine.align_residuals(library, frames, first, span, geom)
+
     def sync_scores_planes_yuv420(self, planes, height, width, layout="i420"):
         """planes: CUDA uint8 [n, 1.5*H*W] (I420 or NV12), even H, W >= 8 -> int64 [n, 64] on device: sync_scores_u8's sums at the
         phases with even py and px, 0 elsewhere -- an odd crop offset does not exist on 4:2:0 planes (engine.svd_sync_scores_yuv420)."""
