@@ -88,6 +88,16 @@ def statement_soft(frame, canvas_hw, geom, L, scale=15.0):
     return ss.regroup(m.reshape(-1), L)
 
 
+def chain_unit_metrics(eng, dev, canvas, g, scale=15):
+    """The chain the fused device calls replace (test_gpu_affine.py, test_gpu_geometry_edges.py): int64 [n, H // 8, W // 8] on the
+    host from engine.warp_affine of the whole canvas + svd_detect_soft with one position per unit, masked by the statement's
+    counting units."""
+    H8, W8 = canvas[0] // 8, canvas[1] // 8
+    warped = eng.warp_affine(dev, g, (8 * H8, 8 * W8))
+    m = eng.svd_detect_soft(warped, H8 * W8, scale=scale).cpu().numpy().reshape(-1, H8, W8)
+    return np.where(units(tuple(dev.shape[1:3]), canvas, g)[None], m, 0)
+
+
 # ---- the attack: a float64 bilinear rotation (and scale) about the centre, on the host ----------------------------------------
 def rotate(frames, angle_deg, step=1.0, out_hw=None):
     """frames u8 [n, H, W, 3] -> u8 [n, h, w, 3], read-only: leak pixel p = (y, x) samples the frame at

@@ -74,13 +74,7 @@ def geometries(leak_hw):
             "shear": SHEAR, "half-turn": (-ONE, 0, (h - 1) << 16, 0, -ONE, (w - 1) << 16)}
 
 
-def chain_unit_metrics(eng, dev, canvas, g, scale=15):
-    """int64 [n, H // 8, W // 8] on the host: warp_affine of the whole canvas + svd_detect_soft with one position per unit, masked
-    by the statement's counting units."""
-    H8, W8 = canvas[0] // 8, canvas[1] // 8
-    warped = eng.warp_affine(dev, g, (8 * H8, 8 * W8))
-    m = eng.svd_detect_soft(warped, H8 * W8, scale=scale).cpu().numpy().reshape(-1, H8, W8)
-    return np.where(af.units(tuple(dev.shape[1:3]), canvas, g)[None], m, 0)
+chain_unit_metrics = af.chain_unit_metrics       # warp_affine of the whole canvas + svd_detect_soft, masked by the statement's units
 
 
 # ---- 1. the warp against the statement ------------------------------------------------------------------------------------------
