@@ -498,17 +498,28 @@ def texture_mask_vec(lum: np.ndarray, ycoef: np.ndarray | None = None, promotion
 # a5 / a7  QIM on coefficient [2][1] of the U blocks
 # --------------------------------------------------------------------------------------
 
-def qim_embed(c21: np.ndarray, step: np.ndarray, bits: np.ndarray) -> np.ndarray:
+def qim_embed(c21: np.ndarray, step: np.ndarray, bits: np.ndarray, sign=None) -> np.ndarray:
     """dct_encoder.py:30-35.  c21 float32, step float64, bits 0/1 -> new c21 float32.
 
     ``abs(c)/step2`` is float32/float64 -> float64 under both promotion regimes;
-    ``np.sign(0) == 0`` so a zero coefficient stays zero and a '1' bit is lost there."""
+    ``np.sign(0) == 0`` so a zero coefficient stays zero and a '1' bit is lost there.
+
+    ``sign`` (TEST INFRASTRUCTURE, not reference semantics): an array broadcastable to ``c21`` with values in
+    {-1, 0, +1}, or NaN for "use np.sign(c)".  Where |c21| is float rounding noise, np.sign(c) is decided by the last
+    bits of the third-party DCT; forcing it states each of the three results the reference can produce there
+    (tests/_ambiguous.py).  ``None`` (default) is the reference, bit for bit."""
     c = np.asarray(c21, dtype=F32)
     step = np.asarray(step, dtype=F64)
     step2 = step + step
     q = np.floor(np.abs(c).astype(F64) / step2) * step2
     q = np.where(np.asarray(bits) == 0, q, q + step)
-    return (np.sign(c).astype(F64) * q).astype(F32)
+    s = np.sign(c).astype(F64)
+    if sign is not None:
+        sign = np.asarray(sign, dtype=F64)
+        if not np.isin(sign[~np.isnan(sign)], (-1.0, 0.0, 1.0)).all():
+            raise ValueError("sign must hold -1, 0, +1 or NaN")
+        s = np.where(np.isnan(sign), s, sign)
+    return (s * q).astype(F32)
 
 
 def qim_read(c21: np.ndarray, step: np.ndarray) -> np.ndarray:
@@ -518,10 +529,13 @@ def qim_read(c21: np.ndarray, step: np.ndarray) -> np.ndarray:
 
 
 class DctEncoderOracle:
-    """dct_encoder.py:4-39.  ``form`` = "vec" | "loop"."""
+    """dct_encoder.py:4-39.  ``form`` = "vec" | "loop".
 
-    def __init__(self, key=None, alpha=20, form: str = "vec", promotion: str = "legacy"):
+    ``sign_override``: None (the reference), or a per-block [rows, cols] array handed to ``qim_embed`` as ``sign``."""
+
+    def __init__(self, key=None, alpha=20, form: str = "vec", promotion: str = "legacy", sign_override=None):
         self.key, self.alpha, self.form, self.promotion = key, alpha, form, promotion
+        self.sign_override = None if sign_override is None else np.asarray(sign_override, dtype=F64)
         self.debug: dict = {}
 
     def read_wm(self, wm):
@@ -555,7 +569,8 @@ class DctEncoderOracle:
                 coeffs = dct8x8(blk)
                 pre[i, j] = coeffs[2, 1]
                 step = self.alpha * mask[i][j]
-                coeffs[2, 1] = qim_embed(coeffs[2, 1], step, self.wm[c])
+                sign = None if self.sign_override is None else self.sign_override[i, j]
+                coeffs[2, 1] = qim_embed(coeffs[2, 1], step, self.wm[c], sign)
                 post[i, j] = coeffs[2, 1]
                 channel[i * 8:i * 8 + 8, j * 8:j * 8 + 8] = idct8x8(coeffs)
                 c += 1
@@ -571,7 +586,9 @@ class DctEncoderOracle:
         ucoef = dct8x8(to_blocks(yuv[:, :, 1]))
         bits = np.asarray(self.wm)[: rows * cols].reshape(rows, cols)
         pre = ucoef[..., 2, 1].copy()
-        post = qim_embed(pre, self.alpha * mask, bits)
+        if self.sign_override is not None and self.sign_override.shape != (rows, cols):
+            raise ValueError(f"sign_override must be [{rows}, {cols}], one entry per block")
+        post = qim_embed(pre, self.alpha * mask, bits, self.sign_override)
         ucoef[..., 2, 1] = post
         from_blocks(idct8x8(ucoef), yuv[:, :, 1])
         self.debug = dict(mask=mask, lum=lum, tex=tex, c21_pre=pre, c21_post=post, ydc=ycoef[..., 0, 0])

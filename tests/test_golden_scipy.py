@@ -13,6 +13,11 @@ float rounding only, so they are compared at this repository's stated budgets, n
   marked u8 pixels .......................... <= 1 LSB on <= 1e-5 of the samples (floor: 1; DwtDctSvd: 2e-5) over
                                               sign-determined (DCT) / determined (DwtDctSvd) blocks; the number of
                                               blocks left out is printed per case (-s / -rP shows it)
+  sign-ambiguous DCT blocks ................. the vector's own sign there is its primitives' noise, so against the vector they
+                                              stay masked; which of the three admissible results (+q, -q, untouched) the HIP
+                                              frame must hold is named by the kernel's own C21, and its pixels are compared
+                                              with that candidate (tests/_ambiguous.py; the vectors themselves are held to
+                                              "one of the three" by test_ambiguous_statement.py)
 
 CPU tests: the oracle against these vectors.  ``-m gpu`` tests: the HIP path (through the C ABI) against them.
 What stays unpinned: OpenCV's and PyWavelets' own float rounding (neither library exists here or on the GPU box)."""
@@ -22,6 +27,7 @@ import warnings
 import numpy as np
 import pytest
 
+import _ambiguous as ab
 import offmark_oracle as orc
 from conftest import ROOT
 
@@ -178,6 +184,12 @@ def test_hip_dct_against_independent_primitive_vectors(eng, case):
     marked = eng.embed(cuda(frame[None]), g["wm"], alpha=alpha)[0].cpu().numpy()
     mask, ok = sign_determined(frame, g["wm"], alpha)
     n_px = check_pixels(marked, g["marked"], mask, 1e-5, case)
+    # the ambiguous blocks: the candidate of the kernel's own sign (the kernel follows the reference as pinned: "legacy")
+    cands = ab.candidates(frame, g["wm"], alpha)
+    assert np.array_equal(cands.amb, ~ok)
+    c21 = eng.debug_planes(cuda(frame), alpha=alpha, wm=g["wm"])["c21_pre"]
+    from test_gpu_parity import _log               # the parity log; test_gpu_parity.py writes it out when it finishes
+    n_sign = ab.assert_marked_by_own_sign(marked, cands, c21, only_ambiguous=True, what=case, log=_log)
     counts, bits = eng.detect(cuda(g["marked"][None]), L, alpha=alpha, want_bits=True)
     bits = bits[0].cpu().numpy()
     n_bits = int((bits.reshape(-1) != g["raw_bits"].reshape(-1)).sum())
@@ -190,7 +202,8 @@ def test_hip_dct_against_independent_primitive_vectors(eng, case):
         cls = DeGrayScale if bool(g["image_payload"]) else DeShuffler
         out = cls(key=int(g["key"])).set_shape(g["payload"].shape).degenerate_counts(counts[0].cpu().numpy(), N)
         assert np.array_equal(np.asarray(out).reshape(-1), np.asarray(g["degenerated"]).reshape(-1))
-    print(f"{case}: {int((~ok).sum())} of {nblk} blocks sign-ambiguous; {n_px} samples 1 LSB off; {n_bits} / {n_own} raw bits differ")
+    print(f"{case}: {int((~ok).sum())} of {nblk} blocks sign-ambiguous (kernel's C21 + / - / 0: {n_sign[0]} / {n_sign[1]} / {n_sign[2]}); "
+          f"{n_px} samples 1 LSB off; {n_bits} / {n_own} raw bits differ")
 
 
 @pytest.mark.gpu
