@@ -649,10 +649,20 @@ def _svd_dct(blocks: np.ndarray, blk: int, inverse: bool = False) -> np.ndarray:
 
 class DwtDctSvdEncoderOracle:
     """Haar LL band of channel 1 -> 4x4 blocks -> DCT -> SVD -> quantise the top singular value.
-    ``np.linalg.svd`` on float32 runs LAPACK in float32, here as in the reference."""
+    ``np.linalg.svd`` on float32 blocks returns float32 factors, here as in the reference.  numpy computes them with its double
+    precision LAPACK loop and rounds the result (linalg.svd casts to its common type, double, first): the factors are the float64
+    decomposition's to half an ulp (held by tests/test_svd_repeated_statement.py)."""
 
-    def __init__(self, key=None, scales=(0, 15, 0), blk=4, form: str = "vec"):
+    def __init__(self, key=None, scales=(0, 15, 0), blk=4, form: str = "vec", pair_override=None):
+        """``pair_override`` (vec form; a test instrument, not reference behaviour): {channel: (u0, v0)} with u0, v0 float32
+        [rows, cols, blk] -- another top singular pair to write back with in place of LAPACK's, in the DCT domain where the
+        reference decomposes; blocks whose u0 row holds a nan keep LAPACK's.  LAPACK's u and v are reflected so that their first
+        column / row becomes the pair (a Householder reflection along the difference: for a pair out of the eigenspaces of a
+        repeated top singular value it acts inside them, so u diag(s) v is still the block); s is kept.  Inside a repeated top
+        singular value every such pair is as valid an answer of the decomposition as LAPACK's (tests/_svd_repeated.py).  LAPACK's
+        own pair, or None, leaves the path untouched."""
         self.key, self.scales, self.blk, self.form = key, list(scales), blk, form
+        self.pair_override = pair_override
         self.debug: dict = {}
         self.debug_ch: dict = {}              # per marked channel: s0, s0_new, gap (vec form)
 
@@ -686,7 +696,21 @@ class DwtDctSvdEncoderOracle:
             else:
                 n = self.blk
                 blocks = to_blocks4(ca, n)
-                u, s, v = np.linalg.svd(_svd_dct(blocks, n))
+                coef = _svd_dct(blocks, n)
+                u, s, v = np.linalg.svd(coef)
+                if self.pair_override is not None and channel in self.pair_override:
+                    u0, v0 = (np.asarray(a, F32) for a in self.pair_override[channel])
+                    wu, wv = u[..., :, 0] - u0, v[..., 0, :] - v0
+                    take = ~np.isnan(u0).any(-1) & ((wu != 0).any(-1) | (wv != 0).any(-1))
+                    for w, mat, left in ((wu, u, True), (wv, v, False)):
+                        w = np.where(take[..., None], w, 0).astype(F64)
+                        ww = np.maximum((w * w).sum(-1), 1e-300)[..., None, None]
+                        m64 = mat.astype(F64)
+                        if left:        # u <- (I - 2 w w^T / w^T w) u
+                            ref = m64 - 2 * w[..., :, None] * np.einsum("...i,...ij->...j", w, m64)[..., None, :] / ww
+                        else:           # v <- v (I - 2 w w^T / w^T w)
+                            ref = m64 - 2 * np.einsum("...ij,...j->...i", m64, w)[..., :, None] * w[..., None, :] / ww
+                        mat[take] = ref[take].astype(F32)
                 s0 = s[..., 0].copy()
                 bits = np.asarray(self.wm)[: rows * cols].reshape(rows, cols)
                 s[..., 0] = ((s[..., 0] // scale + 0.25 + 0.5 * bits) * scale).astype(F32)

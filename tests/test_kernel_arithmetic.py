@@ -414,6 +414,33 @@ def test_svd8_top_triplet_solver_float32_replay():
     assert np.abs(np.linalg.norm(v.astype(np.float64), axis=1) - 1).max() <= 1e-6                   # unit vectors, the fallbacks included
 
 
+def test_svd8_top_replay_stays_inside_the_admitted_set_on_repeated_top_values():
+    """The direction check above holds "where it is defined" (s1 / s0 < 0.99).  Here the same replay of svd8_top is held to the
+    statement of tests/_svd_repeated.py on the families with exactly and nearly repeated top singular values, next to the
+    quantisation thresholds and "below": the marking it produces is within the device tolerances of the nearest result the
+    reference admits (10 x the oracle's own level per family, floor 10 x the control family's, |sigma_top - s0'| <= scale / 64).
+    The twisted factorisation takes SOME unit vector of a repeated eigenvalue's eigenspace, which is all the statement asks:
+    svd8_top needs no counterpart of the 4x4 solver's slow path."""
+    import _svd4_replay as rp
+    import _svd_repeated as sr
+    tol = F(float(re.search(r"kTolTight = ([0-9.eE+-]+)f", open(os.path.join(PKG, "csrc", "svd_kernels.hiph")).read()).group(1)))
+    b = sr.build(8)
+    n = len(b.bits)
+    scales = sr.SCALE_SETS[-1]
+    ref = sr.reference(8, scales)
+    marked = b.frame.copy()
+    for ch in range(3):
+        B = sr.haar_ll(b.frame, ch, 8)[:n]
+        sval, (s0, w, v), iters = _svd8_solve(B, tol=tol)
+        assert iters.max() <= 16 and np.isfinite(v).all()
+        Bm = rp.marked_ll(B, s0, w, v, b.bits, scales[ch])
+        for c in range(n):
+            i, j = divmod(c, sr.TILES_PER_ROW)
+            marked[i * 16:(i + 1) * 16, j * 16:(j + 1) * 16, ch] += np.kron(F(0.5) * (Bm[c] - B[c]), np.ones((2, 2), F))
+    bad = sr.check(b, scales, ref, marked, "replay")
+    assert not bad, "\n".join(bad)
+
+
 def test_fmod_shortcut_is_fmod():
     """fmod_pos (svd_kernels.hiph): trunc of an inflated quotient estimate, one fma, one fix-up == fmodf, bit for bit, for
     0 <= a < 2^20 * b.  Replayed in float32 with a 1-ulp-wrong reciprocal in both directions (v_rcp_f32 is accurate to 1 ulp)."""
