@@ -12,7 +12,9 @@ Tolerances (the reference pins none for this path).  Budgets are ~
   raw per-block bits .................. <= 1e-4 of the blocks (floor: 1 block) vs oracle (ulp-level threshold flips)
   Y DC, C21 ........................... <= 1e-3 absolute on 0..255-scale data
   luminance / texture masks ........... within 2e-6 absolute (float32 rounding of the block mean / of eh carried through
-                                        the float64 formulas) except on <= 1e-4 threshold-flip blocks
+                                        the float64 formulas) except on <= 1e-4 threshold-flip blocks, each of which must be
+                                        tau-unstable by tests/_mask_leaves.py's rule (test_gpu_mask_leaves.py holds every leaf and
+                                        both sides of every threshold at a budget of zero)
   marked u8 pixels .................... <= 1 LSB, on <= 1e-5 of the samples (floor: 1 sample)
 
 Sign-ambiguous blocks: the reference multiplies the quantised magnitude by np.sign(C21)
@@ -32,6 +34,7 @@ import numpy as np
 import pytest
 
 import _ambiguous as ab
+import _mask_leaves as ml
 import offmark_oracle as orc
 from conftest import GOLDEN, golden_cases
 
@@ -174,12 +177,16 @@ def test_debug_planes_against_oracle(eng, case):
     nblk = d["y_dc"].size
     assert np.max(np.abs(d["y_dc"] - enc.debug["ydc"])) <= 1e-3
     assert np.max(np.abs(d["c21_pre"] - enc.debug["c21_pre"])) <= 1e-3
-    for k, ref in (("lum", enc.debug["lum"]), ("tex", enc.debug["tex"])):
+    fl = ml.label_frame(frame, ml.stored_zoo().tau)
+    for k, ref, stab in (("lum", enc.debug["lum"], fl.lum_stab), ("tex", enc.debug["tex"], fl.tex_stab)):
         bad = np.abs(d[k] - ref) > 1e-9 * np.maximum(1, np.abs(ref))
         # texture ramp carries the float32 rounding of eh: allow 2e-6 relative there
         bad &= np.abs(d[k] - ref) > 2e-6
         _log("mask_" + k, bad.sum(), nblk)
         assert bad.sum() <= budget(nblk, BITS_FRAC, floor=0), (k, int(bad.sum()))
+        # a block may be counted against that budget only if the tree cannot decide it: tau-unstable by tests/_mask_leaves.py's
+        # rule (its leaf changes under a perturbation of the features by ten times the oracle's own float32 level)
+        assert not (bad.reshape(-1) & stab.stable).any(), (k, np.flatnonzero(bad.reshape(-1) & stab.stable)[:5])
     same = np.abs(d["step"] - alpha * enc.debug["mask"]) <= 1e-4
     amb = np.abs(enc.debug["c21_pre"]) <= C21_TOL
     post_ok = np.where(amb, np.abs(np.abs(d["c21_post"]) - np.abs(enc.debug["c21_post"])) <= 2e-3,

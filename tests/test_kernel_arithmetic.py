@@ -463,3 +463,157 @@ def test_fmod_shortcut_is_fmod():
         r = fma(-q, b, a)
         r = np.where(r < 0, r + b, r).astype(F)
         assert np.array_equal(r, want), (wrong, np.flatnonzero(r != want)[:5])
+
+
+# ---- texture_code(): the texture tree, branch-free, four float32 threshold constants (common.hiph) -------------------
+def _texture_code_constants():
+    """Everything texture_code() compares with or selects, read from the source text."""
+    body = SRC[SRC.index("float texture_code("):SRC.index("double texture_value(")]
+    K = {}
+    for name in ("TA1", "TB1", "TA2", "TB2"):
+        m = re.search(r"\b" + name + r"\s*=\s*(0x[0-9a-fA-F.]+p[+-]?[0-9]+)f", body)
+        assert m, name
+        K[name] = F(float.fromhex(m.group(1)))
+    for name, pat in (("ACT", r"active = eh > ([0-9.]+)f;"), ("BIG", r"big = eh > ([0-9.]+)f;"), ("GT4", r"\(le_h > ([0-9.]+)f\)"),
+                      ("EPH", r"big \|\| \(e \+ h > ([0-9.]+)f\)"), ("LPE", r"stepped = lpe <= ([0-9.]+)f \?"),
+                      ("LO", r"stepped = lpe <= [0-9.]+f \? ([0-9.]+)f :"), ("HI", r"stepped = lpe <= [0-9.]+f \? [0-9.]+f : ([0-9.]+)f;")):
+        m = re.search(pat, body)
+        assert m, name
+        K[name] = F(float(m.group(1)))
+    # the selects, as written
+    assert "a = big ? TA2 : TA1, b = big ? TB2 : TB1;" in body
+    assert "cond = (l_e >= a && le_h >= b) || (l_e >= b && le_h >= a) || (le_h > 4.f);" in body
+    assert "inner = cond ? stepped : (ramp ? -eh : 1.0f);" in body and "return active ? inner : 1.0f;" in body
+    return K
+
+
+def texture_code_replay(a00abs, dcl, e, eh, K, swap_ab=False, big_ratio_clauses=True, lpe_strict=False, swap_steps=False):
+    """csrc/common.hiph texture_code(), operation for operation, float32, from its second line on (eh = tot - dcl is the
+    feature sums' last operation: test_scaled_dct_flow_graph_reproduces_the_orthonormal_dct).  The keyword arguments are the
+    mutations of the table below, not part of the kernel."""
+    a00abs, dcl, e, eh = (np.asarray(x, F) for x in (a00abs, dcl, e, eh))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        h = eh - e
+        l = dcl - a00abs
+        l_e = l / e
+        lpe = l + e
+        le_h = lpe / h
+        active = eh > K["ACT"]
+        big = eh > K["BIG"]
+        a = np.where(big != swap_ab, K["TA2"], K["TA1"]).astype(F)
+        b = np.where(big != swap_ab, K["TB2"], K["TB1"]).astype(F)
+        ratio = ((l_e >= a) & (le_h >= b)) | ((l_e >= b) & (le_h >= a))
+        if not big_ratio_clauses:
+            ratio &= ~big
+        cond = ratio | (le_h > K["GT4"])
+        ramp = big | (e + h > K["EPH"])
+        lo, hi = (K["HI"], K["LO"]) if swap_steps else (K["LO"], K["HI"])
+        stepped = np.where((lpe < K["LPE"]) if lpe_strict else (lpe <= K["LPE"]), lo, hi).astype(F)
+    inner = np.where(cond, stepped, np.where(ramp, -eh, F(1))).astype(F)
+    return np.where(active, inner, F(1)).astype(F)
+
+
+def texture_value_replay(code):
+    """texture_value(): float64; the ramp's division is a multiplication by the reciprocal of 1510."""
+    code = np.asarray(code, F).astype(np.float64)
+    return np.where(code > 0, code, 1.0 + (1.25 * (-code - 290.0)) * (1.0 / 1510.0))
+
+
+def _same_decisions(code, ref, eh):
+    """The replay's code against the oracle's float64 value: the constants stand for themselves, a negative code is the ramp
+    of exactly this eh (the value within two float64 ulp: reciprocal instead of quotient)."""
+    code, ref = np.asarray(code, F), np.asarray(ref, np.float64)
+    is_ramp = code < 0
+    ok = np.where(is_ramp, (-code == eh) & (np.abs(texture_value_replay(code) - ref) <= 1e-15 * np.abs(ref)), code.astype(np.float64) == ref)
+    return ok
+
+
+def test_texture_code_float32_replay_equals_the_oracle():
+    """Every block of the mask-leaf pool (all feasible leaves, both sides of all 13 comparisons: tests/_mask_leaves.py) against
+    texture_mask_loop, the reference-shaped per-block loop (about 25 s for the 156 k blocks, laid out as one plane), and
+    hand-built feature tuples with non-finite ratios against texture_from_features, its vectorised form."""
+    import _mask_leaves as ml
+    K = _texture_code_constants()
+    p = ml.pool()
+    code = texture_code_replay(p.ft.a00, p.ft.dcl, p.ft.e, p.ft.eh, K)
+    n, cols = p.rgb.shape[0], 512
+    rows = -(-n // cols)
+    yb = np.zeros((rows * cols, 8, 8), F)
+    yb[:n] = orc.bgr2yuv_f32(p.rgb.astype(F))[..., 0]
+    plane = np.zeros((rows * 8, cols * 8), F)
+    orc.from_blocks(yb.reshape(rows, cols, 8, 8), plane)
+    ref = orc.texture_mask_loop(plane).reshape(-1)[:n]
+    assert np.array_equal(ref, p.label.value)                          # and the named-leaf tree, once more, against the loop form
+    ok = _same_decisions(code, ref, p.ft.eh)
+    assert ok.all(), (int((~ok).sum()), np.flatnonzero(~ok)[:5])
+    # hand-built tuples (a00, dcl, eh, e): e = 0 (l / e = inf or nan), h = 0 (eh == e: inf or nan), h < 0, both arms and the
+    # inactive range; l_e exactly at each constant's float32 image, one float32 below and one above, le_h passing and failing
+    T = [(100, 300, 1000, 0), (100, 100, 1000, 0), (100, 300, 500, 0), (100, 100, 500, 0), (0, 0, 200, 0), (0, 0, 100, 0),
+         (100, 300, 1000, 1000), (100, 300, 500, 500), (100, 100, 1000, 1000), (0, 0, 500, 500), (0, 0, 0, 0),
+         (100, 700, 1000, 1200), (100, 300, 500, 600), (100, 5000, 1000, 1100), (100, 100, 300, 400), (50, 60, 200, 300)]
+    for name in ("TA1", "TB1", "TA2", "TB2"):
+        for eh in (F(600), F(1500)):
+            for x in (np.nextafter(K[name], F(0)), K[name], np.nextafter(K[name], F(4))):
+                for e in (F(32), F(64), F(128), F(256)):               # powers of two: l = x * e is exact, l / e == x
+                    l = F(x * e)
+                    assert F(l / e) == x
+                    T.append((F(10), F(l + F(10)), eh, e))
+    a00, dcl, eh, e = (np.array([t[k] for t in T], F) for k in range(4))
+    assert np.array_equal(dcl - a00, (dcl.astype(np.float64) - a00).astype(F))
+    ref = orc.texture_from_features(a00, dcl, eh, e)
+    ok = _same_decisions(texture_code_replay(a00, dcl, e, eh, K), ref, eh)
+    assert ok.all(), [T[i] for i in np.flatnonzero(~ok)]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        assert np.isinf((dcl - a00) / e).any() and np.isnan((dcl - a00) / e).any() and ((eh - e) < 0).any() and ((eh - e) == 0).any()
+    assert len(set(ref.tolist())) >= 4                                   # the tuples are not all on one leaf
+
+
+TEXTURE_MUTATIONS = {
+    # name: (constants to replace, replay keyword arguments, must it change a tau-stable zoo block)
+    "big arm given the small arm's constants": (dict(TA2="TA1", TB2="TB1"), {}, True),
+    "TA2 = TB2 = 1.1": (dict(TA2="TB2"), {}, True),
+    "TA2 = TB2 = 1.4": (dict(TB2="TA2"), {}, True),
+    "big arm's ratio clauses removed": ({}, dict(big_ratio_clauses=False), True),
+    "eh > 1000": (dict(BIG=1000), {}, True),
+    "le_h > 8": (dict(GT4=8), {}, True),
+    "le_h > 3": (dict(GT4=3), {}, True),
+    "lpe <= 500": (dict(LPE=500), {}, True),
+    "eh > 130": (dict(ACT=130), {}, True),
+    "2.3 -> 2.2": (dict(TA1=2.2), {}, True),
+    "a / b selection swapped": ({}, dict(swap_ab=True), True),
+    "1.125 / 1.25 selection swapped": ({}, dict(swap_steps=True), True),
+    "e + h > 300": (dict(EPH=300), {}, True),
+    # differs from the kernel only where lpe == 400 exactly, which no tau-stable block can be: recorded, not required
+    "lpe < 400": ({}, dict(lpe_strict=True), False),
+}
+
+
+def test_texture_mutations_change_tau_stable_zoo_blocks():
+    """The mutation table: every listed mutation of texture_code() changes the value of at least one tau-stable block of each zoo
+    frame, so the zero budget of test_gpu_mask_leaves.py turns red on it; next to it, how few blocks it changes in the fixtures
+    the suite had before (against their 1e-4 budget).  Reported through ml.write_report."""
+    import _mask_leaves as ml
+    K = _texture_code_constants()
+    z = ml.zoo()
+    fx = ml.fixture_features()
+    lines = [f"{'mutation':<42} {'zoo clamped':>12} {'zoo unclamped':>14} {'fixtures over budget':>21} {'fixture blocks changed':>23}"]
+    for name, (repl, kw, required) in TEXTURE_MUTATIONS.items():
+        Km = dict(K)
+        for k, v in repl.items():
+            Km[k] = K[v] if isinstance(v, str) else F(v)
+        changed = []
+        for fl in z.labels:
+            f = [x.reshape(-1) for x in (fl.ft.a00, fl.ft.dcl, fl.ft.e, fl.ft.eh)]
+            d = texture_value_replay(texture_code_replay(*f, Km, **kw)) != texture_value_replay(texture_code_replay(*f, K))
+            changed.append(int((d & fl.tex_stab.stable).sum()))
+        over = total = 0
+        for a00, dcl, eh, e in fx.values():
+            d = texture_value_replay(texture_code_replay(a00, dcl, e, eh, Km, **kw)) != texture_value_replay(texture_code_replay(a00, dcl, e, eh, K))
+            total += int(d.sum())
+            over += int(d.sum() > ml.budget(d.size, 1e-4, floor=0))
+        lines.append(f"{name:<42} {changed[0]:>12} {changed[1]:>14} {over:>14} of {len(fx):<3} {total:>23}")
+        if required:
+            assert min(changed) >= 1, (name, changed)
+        else:
+            assert max(changed) == 0, (name, changed)
+    ml.write_report("mask_leaves_mutations.txt", lines)
