@@ -707,6 +707,44 @@ int ofmk_signature_distances(const uint8_t *a, int m, const uint8_t *b, int N, i
 int ofmk_align_residuals_rgb8(const uint8_t *lib, int N, const uint8_t *leak, int m, int h, int w, int H, int W, const int32_t *first,
                               int span, const ofmk_affine *geom, long long *res, void *stream, const ofmk_opts *opts);
 
+/* ---- reading a leak whose VALUES changed: a tone curve fitted against the SOURCE frames (BUILD EXTENSION) ----------------------
+ * A screen capture, a re-grade or a range mix-up changes a leak's brightness, contrast or gamma, and the DwtDctSvd mark -- the place
+ * of a singular value inside a cell 15 wide -- does not survive a gain of a few percent.  The operator holds the source frames, so the
+ * per-channel curve that takes the leak's values back to the source's can be fitted to them (offmark.tone.read_toned_leak), as the
+ * geometry is: a histogram match for a first registration, then the mean source value per leak value under the registered geometry.
+ * Interleaved u8 RGB; the codec takes no part.  Everything is an integer, so the device equals the NumPy statement (tests/_tone.py)
+ * exactly.
+ *
+ * ofmk_histograms_rgb8: in is device u8 [n][h][w][3]; hist is device int64 [n][3][256], cleared by the call whatever it held:
+ *       hist[f][c][v] = the number of pixels of frame f whose channel c equals v
+ *   Four pixels are fetched as three dwords at any address, the pixels past the last group of four with byte loads; no load leaves
+ *   the frame and no alignment is assumed.  A workgroup counts 16384 pixels into a table in LDS, eight copies of it so that the lanes of
+ *   a wavefront that meet in one bin (flat content) spread over eight words, then adds its non-zero bins with 64-bit atomics.
+ *   Frames in gridDim.y, chunked at 65535.  Required, else OFMK_E_ARG: n >= 1, h, w >= 1 with h*w < 2^28, no null pointer.
+ * ofmk_tone_sums_rgb8: the arguments of ofmk_align_sums_rgb8 -- src is device u8 [n][H][W][3], src[f] the source of leak frame f;
+ *   leak is device u8 [n][h][w][3]; cands is DEVICE memory, ofmk_affine [K] -- and sums is device int64 [n][K][3][256][2], cleared by
+ *   the call whatever it held.  Canvas pixel (y, x) contributes iff it is inside the leak by ofmk_affine's per-pixel rule (no border
+ *   is left out).  With v the byte ofmk_warp_affine_rgb8 would write at (y, x, c) under cands[k]:
+ *       sums[f][k][c][v][0] += 1          sums[f][k][c][v][1] += src[f][y][x][c]
+ *   A candidate out of ofmk_affine's range leaves zeros (the list is not read on the host).  A workgroup owns a tile of 64 x 64
+ *   canvas pixels of one candidate and one frame and leaves at once when the tile lies wholly beyond one edge of the leak; the taps
+ *   are formed as in ofmk_align_sums_rgb8 and no warped frame is written.  It accumulates into a table of 3*256*2 32-bit words in
+ *   LDS (a tile's entries stay below 4096 * 255 < 2^20): a lane adds a run of equal values down its column once, and a wavefront
+ *   whose lanes all add to one bin adds once; then the bins with a count go to sums with 64-bit atomics -- integer adds, so the
+ *   result does not depend on their order.  Candidates in gridDim.y and frames in gridDim.z, chunked at 65535 and below 2^30
+ *   workgroups per launch.  Required, else OFMK_E_ARG: n >= 1, 8 <= H, W <= 4096, h, w >= 1 with h*w < 2^28, K >= 1, n*K < 2^40,
+ *   no null pointer.
+ * ofmk_apply_tone_rgb8: in is device u8 [n][h][w][3]; lut is DEVICE u8 [3][256]; out is device u8 [n][h][w][3], every byte written:
+ *       out[f][y][x][c] = lut[c][in[f][y][x][c]]
+ *   out == in (exactly) is allowed; any other overlap is not.  12 bytes per thread as three dwords at any address, in and out; no
+ *   alignment is assumed.  Required, else OFMK_E_ARG: n >= 1, h, w >= 1 with h*w < 2^28, no null pointer.
+ * The three calls allocate nothing, synchronise nothing and are graph capturable; all are timed as kind 4 (svd); the flags are
+ * ignored. */
+int ofmk_histograms_rgb8(const uint8_t *in, int n, int h, int w, long long *hist, void *stream, const ofmk_opts *opts);
+int ofmk_tone_sums_rgb8(const uint8_t *src, const uint8_t *leak, int n, int h, int w, int H, int W, const ofmk_affine *cands, int K,
+                        long long *sums, void *stream, const ofmk_opts *opts);
+int ofmk_apply_tone_rgb8(const uint8_t *in, int n, int h, int w, const uint8_t *lut, uint8_t *out, void *stream, const ofmk_opts *opts);
+
 /* ---- DeShuffler.degenerate's epilogue for a batch, on the device ---------------------------
  * src/offmark/degenerator/de_shuffler.py:17-22: mean of bits[i::L] (from `counts`), undo the key
  * permutation (`perm` = DeShuffler.payload_idx, device int32 [L]), threshold strictly above the

@@ -55,6 +55,7 @@
 #include "affine_phase_kernels.hiph"
 #include "align_kernels.hiph"
 #include "temporal_kernels.hiph"
+#include "tone_kernels.hiph"
 
 namespace {
 
@@ -2106,6 +2107,82 @@ int ofmk_align_residuals_rgb8(const uint8_t *lib, int N, const uint8_t *leak, in
                           leak + (size_t)f0 * a.leak_stride, first + f0, a, reinterpret_cast<unsigned long long *>(res) + (size_t)f0 * span * 2);
         return OFMK_OK;
     });
+    HIP_TRY(hipGetLastError());
+    return OFMK_OK;
+}
+
+// ---- leaks whose values changed: a tone curve fitted against the source frames (tone_kernels.hiph; build extensions) ----------------
+// hist[f][c][v] = the number of pixels of frame f whose channel c equals v; int64 [n][3][256], cleared here whatever it held.
+int ofmk_histograms_rgb8(const uint8_t *in, int n, int h, int w, long long *hist, void *stream, const ofmk_opts *opts) {
+    if (int orc = check_opts(opts)) return orc;
+    if (n <= 0) return fail(OFMK_E_ARG, "n must be positive%s");
+    if (int rc = check_leak_dims(h, w)) return rc;
+    if (!in || !hist) return fail(OFMK_E_ARG, "null pointer%s");
+    const Ctx cx = make_ctx(stream, opts);
+    HIP_TRY(launch_zero(hist, (size_t)n * kToneBins * sizeof(long long), cx.s));
+    HistArgs a;
+    a.pixels = h * w;
+    a.frame_stride = (size_t)h * w * 3;
+    const int groups = a.pixels >> 2;
+    const unsigned slices = (unsigned)(groups > kHistGroups ? (groups + kHistGroups - 1) / kHistGroups : 1);
+    for_chunks(n, kMaxChunk, [&](int f0, int cf) {
+        ScopedTiming timing(KIND_SVD, cx);
+        OFMK_TIMED_LAUNCH(timing, histograms_rgb8_kernel, dim3(slices, (unsigned)cf), dim3(kThreads), 0, cx.s, in + (size_t)f0 * a.frame_stride,
+                          reinterpret_cast<unsigned long long *>(hist) + (size_t)f0 * kToneBins, a);
+        return OFMK_OK;
+    });
+    HIP_TRY(hipGetLastError());
+    return OFMK_OK;
+}
+
+// sums[f][k][c][v] = (the number of canvas pixels inside the leak where leak frame f warped by cands[k] (DEVICE memory, [K]) shows v in
+// channel c, the sum of source frame f's channel c over them); int64 [n][K][3][256][2], cleared here whatever it held; an out-of-range
+// candidate leaves zeros.  Chunks as ofmk_align_sums_rgb8.
+int ofmk_tone_sums_rgb8(const uint8_t *src, const uint8_t *leak, int n, int h, int w, int H, int W, const ofmk_affine *cands, int K,
+                        long long *sums, void *stream, const ofmk_opts *opts) {
+    if (int orc = check_opts(opts)) return orc;
+    if (int rc = check_dims(n, H, W)) return rc;
+    if (H > kAlignMaxSide || W > kAlignMaxSide) return fail(OFMK_E_ARG, "canvas H, W must be at most 4096%s");
+    if (int rc = check_leak_dims(h, w)) return rc;
+    if (!src || !leak || !cands || !sums) return fail(OFMK_E_ARG, "null pointer%s");
+    if (K < 1) return fail(OFMK_E_ARG, "K must be at least 1%s");
+    if ((long long)n * K >= (1LL << 40)) return fail(OFMK_E_ARG, "n * K must be < 2^40%s");
+    const Ctx cx = make_ctx(stream, opts);
+    HIP_TRY(launch_zero(sums, (size_t)n * K * kToneWords * sizeof(long long), cx.s));
+    ToneSumsArgs a;
+    a.h = h; a.w = w; a.H = H; a.W = W;
+    a.tiles_x = (W + kAlignTile - 1) / kAlignTile;
+    a.K = K;
+    a.leak_stride = (size_t)h * w * 3;
+    a.src_stride = (size_t)H * W * 3;
+    const long long tiles = (long long)a.tiles_x * ((H + kAlignTile - 1) / kAlignTile);
+    const AffineMap *dc = reinterpret_cast<const AffineMap *>(cands);
+    for_chunks(K, kMaxChunk, [&](int k0, int ck) {
+        const long long room = (1LL << 30) / (tiles * ck);                       // workgroups per launch stay below 2^30
+        const int cap = room < 1 ? 1 : room > kMaxChunk ? kMaxChunk : (int)room;
+        return for_chunks(n, cap, [&](int f0, int cf) {
+            ScopedTiming timing(KIND_SVD, cx);
+            OFMK_TIMED_LAUNCH(timing, tone_sums_rgb8_kernel, dim3((unsigned)tiles, (unsigned)ck, (unsigned)cf), dim3(kThreads), 0, cx.s,
+                              src + (size_t)f0 * a.src_stride, leak + (size_t)f0 * a.leak_stride, dc + k0, a,
+                              reinterpret_cast<unsigned long long *>(sums) + ((size_t)f0 * K + k0) * kToneWords);
+            return OFMK_OK;
+        });
+    });
+    HIP_TRY(hipGetLastError());
+    return OFMK_OK;
+}
+
+// out[f][y][x][c] = lut[c][in[f][y][x][c]]: u8 [n][h][w][3], every byte written; lut is DEVICE u8 [3][256]; out == in is allowed.
+int ofmk_apply_tone_rgb8(const uint8_t *in, int n, int h, int w, const uint8_t *lut, uint8_t *out, void *stream, const ofmk_opts *opts) {
+    if (int orc = check_opts(opts)) return orc;
+    if (n <= 0) return fail(OFMK_E_ARG, "n must be positive%s");
+    if (int rc = check_leak_dims(h, w)) return rc;
+    if (!in || !lut || !out) return fail(OFMK_E_ARG, "null pointer%s");
+    const Ctx cx = make_ctx(stream, opts);
+    const size_t bytes = (size_t)n * h * w * 3, steps = (bytes / 12 + kThreads - 1) / kThreads;
+    const unsigned grid = (unsigned)(steps < 1 ? 1 : steps > 32768 ? 32768 : steps);      // beyond that a thread walks several groups
+    ScopedTiming timing(KIND_SVD, cx);
+    OFMK_TIMED_LAUNCH(timing, apply_tone_rgb8_kernel, dim3(grid), dim3(kThreads), 0, cx.s, in, out, lut, bytes);
     HIP_TRY(hipGetLastError());
     return OFMK_OK;
 }

@@ -838,6 +838,52 @@ class DctEngine:
                                                       out.data_ptr(), _hip.current_stream(), self._o()))
         return out
 
+    # -- leaks whose values changed: a tone curve fitted against the source frames (build extension; offmark.tone) ---------------------
+    def histograms(self, frames, out=None):
+        """The per-channel histograms of every frame: uint8 [n, h, w, 3] -> int64 [n, 3, 256], entry [f, c, v] the number of pixels of
+        frame f whose channel c equals v (include/offmark_hip.h: ofmk_histograms_rgb8)."""
+        t = self.torch
+        n, h, w = self._check_frames(frames, t.uint8)
+        out = self._soft(out, 3, 256, copies=n)
+        _hip.check(self.lib.ofmk_histograms_rgb8(frames.data_ptr(), n, h, w, out.data_ptr(), _hip.current_stream(), self._o()))
+        return out
+
+    def tone_sums(self, sources, frames, cands, sums=None):
+        """Per leak value, how many canvas pixels show it and what the source holds there (ofmk_tone_sums_rgb8).  sources: uint8
+        [n, H, W, 3], H, W <= 4096; frames: uint8 [n, h, w, 3]; ``cands``: int64 [K, 6], a tensor on this device or an array (copied
+        there) -> int64 [n, K, 3, 256, 2]: entry [f, k, c, v] is (count, sum of the source's channel c) over the canvas pixels inside
+        the leak where frame f warped by candidate k has v in channel c; a candidate out of range has zeros.  No warped frame is
+        written."""
+        t = self.torch
+        n, H, W = self._check_frames(sources, t.uint8)
+        m, h, w = self._check_frames(frames, t.uint8)
+        if m != n:
+            raise ValueError("one source frame per leak frame")
+        if not isinstance(cands, t.Tensor):
+            cands = t.from_numpy(np.ascontiguousarray(np.asarray(cands, dtype=np.int64)))
+        cands = cands.to(device=self.device, dtype=t.int64).contiguous()
+        if cands.dim() != 2 or cands.shape[1] != 6 or cands.shape[0] < 1:
+            raise ValueError("cands must be int64 [K, 6] with K >= 1")
+        K = int(cands.shape[0])
+        sums = self._buffer("sums", sums, (n, K, 3, 256, 2), t.int64, self.device)
+        _hip.check(self.lib.ofmk_tone_sums_rgb8(sources.data_ptr(), frames.data_ptr(), n, h, w, H, W, cands.data_ptr(), K, sums.data_ptr(),
+                                                _hip.current_stream(), self._o()))
+        return sums
+
+    def apply_tone(self, frames, lut, out=None):
+        """out[f, y, x, c] = lut[c, frames[f, y, x, c]]: uint8 [n, h, w, 3] -> uint8 [n, h, w, 3]; ``lut``: uint8 [3, 256], a tensor on
+        this device or an array (copied there); ``out`` may be ``frames`` itself (ofmk_apply_tone_rgb8)."""
+        t = self.torch
+        n, h, w = self._check_frames(frames, t.uint8)
+        if not isinstance(lut, t.Tensor):
+            lut = t.from_numpy(np.ascontiguousarray(np.asarray(lut, dtype=np.uint8)))
+        lut = lut.to(device=self.device, dtype=t.uint8).contiguous()
+        if tuple(lut.shape) != (3, 256):
+            raise ValueError("lut must be uint8 [3, 256]")
+        out = self._out(out, frames)
+        _hip.check(self.lib.ofmk_apply_tone_rgb8(frames.data_ptr(), n, h, w, lut.data_ptr(), out.data_ptr(), _hip.current_stream(), self._o()))
+        return out
+
     def svd_embed_detect(self, frames, wm, L, scale=15, wm_row=None, out=None, want_bits=False, scales=None, blk=4, counts=None,
                          partial=False):
         t = self.torch

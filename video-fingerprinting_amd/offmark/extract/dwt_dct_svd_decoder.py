@@ -115,6 +115,23 @@ class DwtDctSvdDecoder:
             raise ValueError("the library frames must have the canvas's size")
         return self.engine.align_residuals(library, frames, first, span, geom)
 
+    # -- leaks whose brightness, contrast or gamma changed (build extension: offmark.tone.read_toned_leak) -----------------------------
+    def histograms_u8(self, frames):
+        """frames: CUDA uint8 [n, h, w, 3] -> int64 [n, 3, 256] on device, the per-channel histograms (engine.histograms)."""
+        return self.engine.histograms(frames)
+
+    def tone_sums_u8(self, sources, frames, canvas_hw, cands):
+        """sources: CUDA uint8 [n, H, W, 3] with (H, W) = canvas_hw, frames: CUDA uint8 [n, h, w, 3], cands: int64 [K, 6] -> int64
+        [n, K, 3, 256, 2] on device: per leak value the count and the sum of the source's values (engine.tone_sums)."""
+        if tuple(int(v) for v in sources.shape[1:3]) != (int(canvas_hw[0]), int(canvas_hw[1])):
+            raise ValueError("the source frames must have the canvas's size")
+        return self.engine.tone_sums(sources, frames, cands)
+
+    def apply_tone_u8(self, frames, lut):
+        """frames: CUDA uint8 [n, h, w, 3], lut: uint8 [3, 256] -> CUDA uint8 [n, h, w, 3], lut[c][value] per channel
+        (engine.apply_tone)."""
+        return self.engine.apply_tone(frames, lut)
+
     def sync_scores_planes_yuv420(self, planes, height, width, layout="i420"):
         """planes: CUDA uint8 [n, 1.5*H*W] (I420 or NV12), even H, W >= 8 -> int64 [n, 64] on device: sync_scores_u8's sums at the
         phases with even py and px, 0 elsewhere -- an odd crop offset does not exist on 4:2:0 planes (engine.svd_sync_scores_yuv420)."""
