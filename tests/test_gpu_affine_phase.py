@@ -114,6 +114,28 @@ def test_small_canvases(eng, canvas):
     assert (units[0] == (canvas[0] // 8) * (canvas[1] // 8)).all() and got[:, [0, 1, 3]].all()
 
 
+def test_candidates_past_a_launch_chunk(eng):
+    """More candidates than one launch takes (65535 sit in gridDim.y): rows 65533.. (two before the chunk edge, two past it) and a
+    strided sample of the earlier rows, scores and units, equal the same candidates in a call of their own, so the second launch's
+    candidate offset and both output offsets (* 64) are right.  The 40 x 8 canvas of test_small_canvases under a 48 x 16 leak, which
+    holds every shifted unit; n = 1: the identity with sub-pixel offsets, four distinct small shears around the edge.  The frame side
+    of the chunk rule (launches of fewer frames once n * K workgroups pass 2^30) is not tested: it needs n * K >= 2^30 outputs."""
+    import torch
+    K, edge, canvas = 65535 + 2, 65535, (40, 8)
+    g = torch.Generator(device="cuda")
+    g.manual_seed(21)
+    frames = torch.randint(0, 256, (1, 48, 16, 3), dtype=torch.uint8, device="cuda", generator=g)
+    k = np.arange(K, dtype=np.int64)
+    cands = np.stack([np.full(K, ONE), 0 * k, 3 * (k % 251), 0 * k, np.full(K, ONE), 5 * (k % 241)], axis=1)
+    cands[edge - 2:] = [(ONE, s, 1 << 15, -s, ONE, 1 << 16) for s in (200, 400, 600, 800)]
+    cands = torch.from_numpy(cands).cuda()
+    full, full_units = eng.svd_affine_phase_scores(frames, canvas, cands, scores=garbage((1, K, 64)), units=garbage((K, 64)))
+    for rows in (slice(edge - 2, K), torch.arange(0, edge - 2, 4099, device="cuda")):
+        own, own_units = eng.svd_affine_phase_scores(frames, canvas, cands[rows].contiguous())
+        assert torch.equal(full[:, rows], own) and torch.equal(full_units[rows], own_units)
+    assert (full_units[:edge - 2] == 5).all() and (full_units[edge:] > 0).all() and full[0, edge:].any(dim=1).all()
+
+
 def test_a_canvas_larger_than_the_leak(eng):
     """136 x 200 pixel origins are 5 x 7 rectangles over a 57 x 91 leak: rectangles wholly beyond an edge of the leak (they leave
     early), rectangles the leak's edge runs through, and under the last candidate (a canvas pixel steps 2.2 leak pixels) only a

@@ -95,6 +95,31 @@ def test_small_canvases(eng, canvas):
     assert (want[:, 0, 28] == (min(canvas[0], 57) - 2 + (canvas[0] > 57)) * (min(canvas[1], 91) - 2 + (canvas[1] > 91))).all()
 
 
+def edge_candidates(K):
+    """K candidates for an 8 x 8 leak on an 8 x 8 canvas: the identity with sub-pixel offsets, and around the launch-chunk edge (65535
+    candidates sit in gridDim.y) four distinct small shears, two before it and two past it.  All in range, every pixel inside."""
+    k = np.arange(K, dtype=np.int64)
+    cands = np.stack([np.full(K, ONE), 0 * k, 3 * (k % 251), 0 * k, np.full(K, ONE), 5 * (k % 241)], axis=1)
+    cands[65533:65537] = [(ONE, s, 1 << 14, -s, ONE, 1 << 14) for s in (200, 400, 600, 800)]
+    return cands
+
+
+def test_sums_of_candidates_past_a_launch_chunk(eng):
+    """More candidates than one launch takes: rows 65533.. (two before the chunk edge, two past it) and a strided sample of the
+    earlier rows equal the same candidates in a call of their own, so the second launch's candidate and output offsets (* 29) are
+    right.  n = 1; the frame side of the chunk rule (launches of fewer frames once n * K workgroups pass 2^30) is not tested: it
+    needs n * K >= 2^30 outputs."""
+    import torch
+    K, edge = 65535 + 2, 65535
+    sources, frames = cuda(noise((1, 8, 8, 3), 31)), cuda(noise((1, 8, 8, 3), 32))
+    cands = torch.from_numpy(edge_candidates(K)).cuda()
+    full = eng.align_sums(sources, frames, cands, sums=garbage((1, K, 29)))
+    assert torch.equal(full[:, edge - 2:], eng.align_sums(sources, frames, cands[edge - 2:].contiguous()))
+    sample = torch.arange(0, edge - 2, 4099, device="cuda")
+    assert torch.equal(full[:, sample], eng.align_sums(sources, frames, cands[sample].contiguous()))
+    assert full[0, edge:, :28].any(dim=1).all() and (full[0, :, 28] == 36).all()             # 6 x 6 contributing pixels each
+
+
 def test_a_canvas_twice_the_leak(eng):
     """136 x 200 canvas pixels are 3 x 4 tiles over a 57 x 91 leak: tiles wholly beyond an edge of the leak leave early, the leak's
     edges run through others."""

@@ -159,6 +159,26 @@ def test_sums_at_odd_addresses_and_on_a_canvas_twice_the_leak(eng):
     assert want[:, :3, :, :, 0].any() and not want[:, 3].any() and (want[..., 0].sum(axis=3) <= 56 * 90).all()
 
 
+def test_sums_of_candidates_past_a_launch_chunk(eng):
+    """More candidates than one launch takes (65535 sit in gridDim.y): rows 65533.. (two before the chunk edge, two past it) and a
+    strided sample of the earlier rows equal the same candidates in a call of their own, so the second launch's candidate and output
+    offsets (* 1536) are right.  An 8 x 8 leak on an 8 x 8 canvas, n = 1: the identity with sub-pixel offsets, four distinct small
+    shears around the edge; every pixel inside.  The output is 0.8 GB: one buffer, compared in slices.  The frame side of the chunk
+    rule (launches of fewer frames once n * K workgroups pass 2^30) is not tested: it needs n * K >= 2^30 outputs."""
+    import torch
+    K, edge = 65535 + 2, 65535
+    sources, frames = cuda(noise((1, 8, 8, 3), 33)), cuda(noise((1, 8, 8, 3), 34))
+    k = np.arange(K, dtype=np.int64)
+    cands = np.stack([np.full(K, ONE), 0 * k, 3 * (k % 251), 0 * k, np.full(K, ONE), 5 * (k % 241)], axis=1)
+    cands[edge - 2:] = [(ONE, s, 1 << 14, -s, ONE, 1 << 14) for s in (200, 400, 600, 800)]
+    cands = torch.from_numpy(cands).cuda()
+    full = eng.tone_sums(sources, frames, cands, sums=garbage((1, K, 3, 256, 2)))
+    assert torch.equal(full[:, edge - 2:], eng.tone_sums(sources, frames, cands[edge - 2:].contiguous()))
+    sample = torch.arange(0, edge - 2, 4099, device="cuda")
+    assert torch.equal(full[:, sample], eng.tone_sums(sources, frames, cands[sample].contiguous()))
+    assert (full[0, edge:, :, :, 0].sum(dim=2) == 64).all()                    # past the edge: all 64 pixels counted in every channel
+
+
 # ---- 3. apply tone ------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("shape", [(3, 9, 13), (1, 1, 1), (2, 72, 104), (1, 2, 2)])
 def test_apply_tone_equals_the_statement(eng, shape):

@@ -848,7 +848,7 @@ int check_leak_dims(int h, int w) {
     return OFMK_OK;
 }
 
-int check_warp_map(const ofmk_warp *geom, WarpMap &m) {
+int check_map(const ofmk_warp *geom, WarpMap &m) {
     m.ay = geom->ay; m.by = geom->by; m.ax = geom->ax; m.bx = geom->bx;
     if (!warp_map_ok(m)) return fail(OFMK_E_ARG, "ofmk_warp: ay, ax must be in [2^12, 2^20] and |by|, |bx| <= 2^48%s");
     return OFMK_OK;
@@ -871,7 +871,7 @@ void warp_axis_units(long long a, long long b, int len, int units, int &u0, int 
     u1 = lo;
 }
 
-void warp_rect(const WarpMap &m, int h, int w, int H, int W, int out[4]) {
+void units_rect(const WarpMap &m, int h, int w, int H, int W, int out[4]) {
     int i0, i1, j0, j1;
     warp_axis_units(m.ay, m.by, h, H / 8, i0, i1);
     warp_axis_units(m.ax, m.bx, w, W / 8, j0, j1);
@@ -882,7 +882,7 @@ void warp_rect(const WarpMap &m, int h, int w, int H, int W, int out[4]) {
 // ---- rotated leaks (affine_kernels.hiph) ---------------------------------------------------------------------------------------
 static_assert(sizeof(AffineMap) == sizeof(ofmk_affine) && sizeof(ofmk_affine) == 48, "ofmk_affine is six int64");
 
-int check_affine_map(const ofmk_affine *geom, AffineMap &m) {
+int check_map(const ofmk_affine *geom, AffineMap &m) {
     m.ayy = geom->ayy; m.ayx = geom->ayx; m.by = geom->by; m.axy = geom->axy; m.axx = geom->axx; m.bx = geom->bx;
     if (!affine_map_ok(m))
         return fail(OFMK_E_ARG, "ofmk_affine: coefficients must be in [-2^20, 2^20], |by|, |bx| <= 2^48 and |ayy*axx - ayx*axy| >= 2^24%s");
@@ -904,7 +904,7 @@ void affine_bound(long long a, long long c, long long &lo, long long &hi) {
 
 // out = {i0, i1, j0, j1, count}: the bounding rectangle of the counting units and how many count; all 0 when none does.  Each of a
 // unit's 16 conditions (4 corner pixels x 4 edges of the leak) is linear in j, so a row of units counts on an interval of j.
-void affine_rect(const AffineMap &m, int h, int w, int H, int W, int out[5]) {
+void units_rect(const AffineMap &m, int h, int w, int H, int W, int out[5]) {
     const int rows = H / 8, cols = W / 8;
     int i0 = rows, i1 = 0, j0 = cols, j1 = 0, count = 0;
     for (int i = 0; i < rows; ++i) {
@@ -923,6 +923,116 @@ void affine_rect(const AffineMap &m, int h, int w, int H, int W, int out[5]) {
         count += (int)(hi - lo + 1);
     }
     out[0] = count ? i0 : 0; out[1] = i1; out[2] = count ? j0 : 0; out[3] = j1; out[4] = count;
+}
+
+// ---- what the leak-geometry calls share, under either map (WarpMap with ofmk_warp, AffineMap with ofmk_affine) ---------------------
+int check_canvas(int H, int W) {
+    if (H < 1 || W < 1 || (long long)H * W >= (1LL << 28)) return fail(OFMK_E_ARG, "canvas H, W must be positive with H*W < 2^28%s");
+    return OFMK_OK;
+}
+
+int check_out_rect(int Hout, int Wout, int oy, int ox) {
+    if (Hout < 1 || Wout < 1 || (long long)Hout * Wout >= (1LL << 28)) return fail(OFMK_E_ARG, "Hout, Wout must be positive with Hout*Wout < 2^28%s");
+    if (oy < 0 || ox < 0 || oy >= (1 << 28) || ox >= (1 << 28)) return fail(OFMK_E_ARG, "oy, ox must be in [0, 2^28)%s");
+    return OFMK_OK;
+}
+
+// The checks of the calls that take a candidate list: ptrs = "every pointer is non-null"; max_side > 0 bounds the canvas sides, `why` ends its message.
+int check_search_args(const ofmk_opts *opts, int n, int h, int w, int H, int W, bool ptrs, int K, int max_side = 0, const char *why = "") {
+    if (int orc = check_opts(opts)) return orc;
+    if (int rc = check_dims(n, H, W)) return rc;
+    if (max_side > 0 && (H > max_side || W > max_side)) return fail(OFMK_E_ARG, "canvas H, W must be at most 4096%s", why);
+    if (int rc = check_leak_dims(h, w)) return rc;
+    if (!ptrs) return fail(OFMK_E_ARG, "null pointer%s");
+    if (K < 1) return fail(OFMK_E_ARG, "K must be at least 1%s");
+    if ((long long)n * K >= (1LL << 40)) return fail(OFMK_E_ARG, "n * K must be < 2^40%s");
+    return OFMK_OK;
+}
+
+// Candidates [0, K) in gridDim.y and frames [0, n) in gridDim.z, both in chunks of at most kMaxChunk, with units_per_pair workgroups
+// per frame and candidate in gridDim.x: body(k0, ck, f0, cf), until one returns an error code.
+template <class Body>
+int for_cand_frame_chunks(long long units_per_pair, int K, int n, Body &&body) {
+    return for_chunks(K, kMaxChunk, [&](int k0, int ck) {
+        const long long room = (1LL << 30) / (units_per_pair * ck);              // workgroups per launch stay below 2^30
+        const int cap = room < 1 ? 1 : room > kMaxChunk ? kMaxChunk : (int)room;
+        return for_chunks(n, cap, [&](int f0, int cf) { return body(k0, ck, f0, cf); });
+    });
+}
+
+// out = the counting rectangle of canvas units under *geom (units_rect): ofmk_warp_units / ofmk_affine_units.
+template <class Map, class Geom>
+int map_units(int h, int w, int H, int W, const Geom *geom, int *out) {
+    if (!geom || !out) return fail(OFMK_E_ARG, "null pointer%s");
+    if (int rc = check_leak_dims(h, w)) return rc;
+    if (int rc = check_canvas(H, W)) return rc;
+    Map m;
+    if (int rc = check_map(geom, m)) return rc;
+    units_rect(m, h, w, H, W, out);
+    return OFMK_OK;
+}
+
+// The leak resampled onto a canvas rectangle: ofmk_warp_rgb8 (Args = WarpArgs; takes no timing pair) / ofmk_warp_affine_rgb8.
+template <class Args, auto Kernel, bool kTimed, class Geom>
+int warp_frames(const uint8_t *in, int n, int h, int w, uint8_t *out, int Hout, int Wout, int oy, int ox, const Geom *geom, void *stream,
+                const ofmk_opts *opts) {
+    if (int orc = check_opts(opts)) return orc;
+    if (n <= 0) return fail(OFMK_E_ARG, "n must be positive%s");
+    if (!in || !out || !geom) return fail(OFMK_E_ARG, "null pointer%s");
+    if (int rc = check_leak_dims(h, w)) return rc;
+    if (int rc = check_out_rect(Hout, Wout, oy, ox)) return rc;
+    Args a;
+    if (int rc = check_map(geom, a.m)) return rc;
+    Ctx cx = make_ctx(stream, opts);
+    if (!kTimed) cx.t = nullptr;
+    a.h = h; a.w = w; a.Hout = Hout; a.Wout = Wout; a.oy = oy; a.ox = ox;
+    a.in_stride = (size_t)h * w * 3;
+    a.out_stride = (size_t)Hout * Wout * 3;
+    for_chunks(n, kMaxChunk, [&](int f0, int cf) {
+        ScopedTiming timing(KIND_SVD, cx);
+        OFMK_TIMED_LAUNCH(timing, Kernel, grid_2d(Hout * Wout, cf), dim3(kThreads), 0, cx.s, in + (size_t)f0 * a.in_stride,
+                          out + (size_t)f0 * a.out_stride, a);
+        return OFMK_OK;
+    });
+    HIP_TRY(hipGetLastError());
+    return OFMK_OK;
+}
+
+// The soft read-out of the counting units of the leak under *geom: ofmk_svd_detect_soft_warp_rgb8 / ofmk_svd_detect_soft_affine_rgb8.
+template <class Args, auto Kernel, class Geom>
+int svd_detect_soft_mapped(const uint8_t *in, int n, int h, int w, int H, int W, const Geom *geom, int L, const double *scales, int blk,
+                           long long *soft, void *stream, const ofmk_opts *opts) {
+    if (int orc = check_opts(opts)) return orc;
+    if (int rc = check_soft_args(in, n, H, W, L, soft)) return rc;
+    if (int rc = check_leak_dims(h, w)) return rc;
+    if (!geom) return fail(OFMK_E_ARG, "null pointer%s");
+    Args a;
+    if (int rc = check_map(geom, a.m)) return rc;
+    SvdArgs sa;
+    if (int rc = check_resync_scales(sa, scales, blk, false)) return rc;
+    const Ctx cx = make_ctx(stream, opts);
+    HIP_TRY(launch_zero(soft, (size_t)n * L * sizeof(long long), cx.s));
+    int r[5];
+    units_rect(a.m, h, w, H, W, r);
+    if (!(sa.scales[1] > 0.f) || r[1] == r[0]) return OFMK_OK;                   // no unit counts: both rectangles are then all 0
+    a.h = h; a.w = w;
+    a.i0 = r[0]; a.j0 = r[2];
+    a.cols = r[3] - r[2];
+    a.nunits = (r[1] - r[0]) * a.cols;
+    a.canvas_cols = W / 8;
+    a.L = L;
+    a.frame_stride = (size_t)h * w * 3;
+    a.scale = sa.scales[1];
+    for_chunks(n, kMaxChunk, [&](int f0, int cf) {
+        ScopedTiming timing(KIND_SVD, cx);
+        Args ac = a;
+        ac.frames = cf;
+        ac.soft = soft + (size_t)f0 * L;
+        OFMK_TIMED_LAUNCH(timing, Kernel, xcd_grid(a.nunits, cf), dim3(kThreads), 0, cx.s, in + (size_t)f0 * a.frame_stride, ac);
+        return OFMK_OK;
+    });
+    HIP_TRY(hipGetLastError());
+    return OFMK_OK;
 }
 
 // ---- C marked copies of the same frames (copies_kernels.hiph) -------------------------------------------------------
@@ -1725,49 +1835,20 @@ int ofmk_svd_detect_soft_window_rgb8(const uint8_t *in, int n, int H, int W, int
 // ---- rescaled leaks (warp_kernels.hiph; build extensions, not reference semantics) ---------------------------------------------
 // Host only: the counting rectangle of canvas units, out = {i0, i1, j0, j1}, all 0 when no unit counts.
 int ofmk_warp_units(int h, int w, int H, int W, const ofmk_warp *geom, int out[4]) {
-    if (!geom || !out) return fail(OFMK_E_ARG, "null pointer%s");
-    if (int rc = check_leak_dims(h, w)) return rc;
-    if (H < 1 || W < 1 || (long long)H * W >= (1LL << 28)) return fail(OFMK_E_ARG, "canvas H, W must be positive with H*W < 2^28%s");
-    WarpMap m;
-    if (int rc = check_warp_map(geom, m)) return rc;
-    warp_rect(m, h, w, H, W, out);
-    return OFMK_OK;
+    return map_units<WarpMap>(h, w, H, W, geom, out);
 }
 
 // The leak resampled onto the canvas rectangle [oy, oy + Hout) x [ox, ox + Wout): u8 [n][Hout][Wout][3], every byte written.
 int ofmk_warp_rgb8(const uint8_t *in, int n, int h, int w, uint8_t *out, int Hout, int Wout, int oy, int ox, const ofmk_warp *geom,
                    void *stream, const ofmk_opts *opts) {
-    if (int orc = check_opts(opts)) return orc;
-    if (n <= 0) return fail(OFMK_E_ARG, "n must be positive%s");
-    if (!in || !out || !geom) return fail(OFMK_E_ARG, "null pointer%s");
-    if (int rc = check_leak_dims(h, w)) return rc;
-    if (Hout < 1 || Wout < 1 || (long long)Hout * Wout >= (1LL << 28)) return fail(OFMK_E_ARG, "Hout, Wout must be positive with Hout*Wout < 2^28%s");
-    if (oy < 0 || ox < 0 || oy >= (1 << 28) || ox >= (1 << 28)) return fail(OFMK_E_ARG, "oy, ox must be in [0, 2^28)%s");
-    WarpArgs a;
-    if (int rc = check_warp_map(geom, a.m)) return rc;
-    const Ctx cx = make_ctx(stream, opts);
-    a.h = h; a.w = w; a.Hout = Hout; a.Wout = Wout; a.oy = oy; a.ox = ox;
-    a.in_stride = (size_t)h * w * 3;
-    a.out_stride = (size_t)Hout * Wout * 3;
-    for_chunks(n, kMaxChunk, [&](int f0, int cf) {
-        hipLaunchKernelGGL(warp_rgb8_kernel, grid_2d(Hout * Wout, cf), dim3(kThreads), 0, cx.s, in + (size_t)f0 * a.in_stride,
-                           out + (size_t)f0 * a.out_stride, a);
-        return OFMK_OK;
-    });
-    HIP_TRY(hipGetLastError());
-    return OFMK_OK;
+    return warp_frames<WarpArgs, warp_rgb8_kernel, false>(in, n, h, w, out, Hout, Wout, oy, ox, geom, stream, opts);
 }
 
 // scores[f][k] = sum of |unit metric| over the counting units of frame f warped by cands[k] (DEVICE memory, [K]); int64 [n][K],
 // cleared here whatever it held.  Candidates sit in gridDim.y and frames in gridDim.z, both in chunks of at most 65535.
 int ofmk_svd_warp_scores_rgb8(const uint8_t *in, int n, int h, int w, int H, int W, const ofmk_warp *cands, int K, const double *scales,
                               int blk, long long *scores, void *stream, const ofmk_opts *opts) {
-    if (int orc = check_opts(opts)) return orc;
-    if (int rc = check_dims(n, H, W)) return rc;
-    if (int rc = check_leak_dims(h, w)) return rc;
-    if (!in || !cands || !scores) return fail(OFMK_E_ARG, "null pointer%s");
-    if (K < 1) return fail(OFMK_E_ARG, "K must be at least 1%s");
-    if ((long long)n * K >= (1LL << 40)) return fail(OFMK_E_ARG, "n * K must be < 2^40%s");
+    if (int rc = check_search_args(opts, n, h, w, H, W, in && cands && scores, K)) return rc;
     SvdArgs sa;
     if (int rc = check_resync_scales(sa, scales, blk, true)) return rc;
     const Ctx cx = make_ctx(stream, opts);
@@ -1781,16 +1862,11 @@ int ofmk_svd_warp_scores_rgb8(const uint8_t *in, int n, int h, int w, int H, int
     a.scale = sa.scales[1];
     const long long tiles = (long long)a.tiles_x * ((a.rows + kWarpTileH - 1) / kWarpTileH);
     const WarpMap *dc = reinterpret_cast<const WarpMap *>(cands);
-    for_chunks(K, kMaxChunk, [&](int k0, int ck) {
-        const long long room = (1LL << 30) / (tiles * ck);                       // workgroups per launch stay below 2^30
-        const int cap = room < 1 ? 1 : room > kMaxChunk ? kMaxChunk : (int)room;
-        return for_chunks(n, cap, [&](int f0, int cf) {
-            ScopedTiming timing(KIND_SVD, cx);
-            OFMK_TIMED_LAUNCH(timing, svd_warp_scores_rgb8_kernel, dim3((unsigned)tiles, (unsigned)ck, (unsigned)cf), dim3(kThreads), 0, cx.s,
-                              in + (size_t)f0 * a.frame_stride, dc + k0, a,
-                              reinterpret_cast<unsigned long long *>(scores) + (size_t)f0 * K + k0);
-            return OFMK_OK;
-        });
+    for_cand_frame_chunks(tiles, K, n, [&](int k0, int ck, int f0, int cf) {
+        ScopedTiming timing(KIND_SVD, cx);
+        OFMK_TIMED_LAUNCH(timing, svd_warp_scores_rgb8_kernel, dim3((unsigned)tiles, (unsigned)ck, (unsigned)cf), dim3(kThreads), 0, cx.s,
+                          in + (size_t)f0 * a.frame_stride, dc + k0, a, reinterpret_cast<unsigned long long *>(scores) + (size_t)f0 * K + k0);
+        return OFMK_OK;
     });
     HIP_TRY(hipGetLastError());
     return OFMK_OK;
@@ -1800,86 +1876,26 @@ int ofmk_svd_warp_scores_rgb8(const uint8_t *in, int n, int h, int w, int H, int
 // int64 [n][L], cleared here.  scales[1] <= 0 or no counting unit: all zeros.
 int ofmk_svd_detect_soft_warp_rgb8(const uint8_t *in, int n, int h, int w, int H, int W, const ofmk_warp *geom, int L, const double *scales,
                                    int blk, long long *soft, void *stream, const ofmk_opts *opts) {
-    if (int orc = check_opts(opts)) return orc;
-    if (int rc = check_soft_args(in, n, H, W, L, soft)) return rc;
-    if (int rc = check_leak_dims(h, w)) return rc;
-    if (!geom) return fail(OFMK_E_ARG, "null pointer%s");
-    WarpReadArgs a;
-    if (int rc = check_warp_map(geom, a.m)) return rc;
-    SvdArgs sa;
-    if (int rc = check_resync_scales(sa, scales, blk, false)) return rc;
-    const Ctx cx = make_ctx(stream, opts);
-    HIP_TRY(launch_zero(soft, (size_t)n * L * sizeof(long long), cx.s));
-    int r[4];
-    warp_rect(a.m, h, w, H, W, r);
-    if (!(sa.scales[1] > 0.f) || r[1] == r[0]) return OFMK_OK;
-    a.h = h; a.w = w;
-    a.i0 = r[0]; a.j0 = r[2];
-    a.cols = r[3] - r[2];
-    a.nunits = (r[1] - r[0]) * a.cols;
-    a.canvas_cols = W / 8;
-    a.L = L;
-    a.frame_stride = (size_t)h * w * 3;
-    a.scale = sa.scales[1];
-    for_chunks(n, kMaxChunk, [&](int f0, int cf) {
-        ScopedTiming timing(KIND_SVD, cx);
-        WarpReadArgs ac = a;
-        ac.frames = cf;
-        ac.soft = soft + (size_t)f0 * L;
-        OFMK_TIMED_LAUNCH(timing, svd_soft_warp_rgb8_kernel, xcd_grid(a.nunits, cf), dim3(kThreads), 0, cx.s, in + (size_t)f0 * a.frame_stride, ac);
-        return OFMK_OK;
-    });
-    HIP_TRY(hipGetLastError());
-    return OFMK_OK;
+    return svd_detect_soft_mapped<WarpReadArgs, svd_soft_warp_rgb8_kernel>(in, n, h, w, H, W, geom, L, scales, blk, soft, stream, opts);
 }
 
 // ---- rotated leaks (affine_kernels.hiph; build extensions, not reference semantics) --------------------------------------------
 // Host only: out = {i0, i1, j0, j1, count}, the bounding rectangle of the counting canvas units and their number; all 0 when none counts.
 int ofmk_affine_units(int h, int w, int H, int W, const ofmk_affine *geom, int out[5]) {
-    if (!geom || !out) return fail(OFMK_E_ARG, "null pointer%s");
-    if (int rc = check_leak_dims(h, w)) return rc;
-    if (H < 1 || W < 1 || (long long)H * W >= (1LL << 28)) return fail(OFMK_E_ARG, "canvas H, W must be positive with H*W < 2^28%s");
-    AffineMap m;
-    if (int rc = check_affine_map(geom, m)) return rc;
-    affine_rect(m, h, w, H, W, out);
-    return OFMK_OK;
+    return map_units<AffineMap>(h, w, H, W, geom, out);
 }
 
 // The leak resampled onto the canvas rectangle [oy, oy + Hout) x [ox, ox + Wout): u8 [n][Hout][Wout][3], every byte written.
 int ofmk_warp_affine_rgb8(const uint8_t *in, int n, int h, int w, uint8_t *out, int Hout, int Wout, int oy, int ox, const ofmk_affine *geom,
                           void *stream, const ofmk_opts *opts) {
-    if (int orc = check_opts(opts)) return orc;
-    if (n <= 0) return fail(OFMK_E_ARG, "n must be positive%s");
-    if (!in || !out || !geom) return fail(OFMK_E_ARG, "null pointer%s");
-    if (int rc = check_leak_dims(h, w)) return rc;
-    if (Hout < 1 || Wout < 1 || (long long)Hout * Wout >= (1LL << 28)) return fail(OFMK_E_ARG, "Hout, Wout must be positive with Hout*Wout < 2^28%s");
-    if (oy < 0 || ox < 0 || oy >= (1 << 28) || ox >= (1 << 28)) return fail(OFMK_E_ARG, "oy, ox must be in [0, 2^28)%s");
-    AffineWarpArgs a;
-    if (int rc = check_affine_map(geom, a.m)) return rc;
-    const Ctx cx = make_ctx(stream, opts);
-    a.h = h; a.w = w; a.Hout = Hout; a.Wout = Wout; a.oy = oy; a.ox = ox;
-    a.in_stride = (size_t)h * w * 3;
-    a.out_stride = (size_t)Hout * Wout * 3;
-    for_chunks(n, kMaxChunk, [&](int f0, int cf) {
-        ScopedTiming timing(KIND_SVD, cx);
-        OFMK_TIMED_LAUNCH(timing, warp_affine_rgb8_kernel, grid_2d(Hout * Wout, cf), dim3(kThreads), 0, cx.s, in + (size_t)f0 * a.in_stride,
-                          out + (size_t)f0 * a.out_stride, a);
-        return OFMK_OK;
-    });
-    HIP_TRY(hipGetLastError());
-    return OFMK_OK;
+    return warp_frames<AffineWarpArgs, warp_affine_rgb8_kernel, true>(in, n, h, w, out, Hout, Wout, oy, ox, geom, stream, opts);
 }
 
 // scores[f][k] = sum of |unit metric| over the counting units of frame f warped by cands[k] (DEVICE memory, [K]); int64 [n][K],
 // cleared here whatever it held.  Candidates sit in gridDim.y and frames in gridDim.z, both in chunks of at most 65535.
 int ofmk_svd_affine_scores_rgb8(const uint8_t *in, int n, int h, int w, int H, int W, const ofmk_affine *cands, int K, const double *scales,
                                 int blk, long long *scores, void *stream, const ofmk_opts *opts) {
-    if (int orc = check_opts(opts)) return orc;
-    if (int rc = check_dims(n, H, W)) return rc;
-    if (int rc = check_leak_dims(h, w)) return rc;
-    if (!in || !cands || !scores) return fail(OFMK_E_ARG, "null pointer%s");
-    if (K < 1) return fail(OFMK_E_ARG, "K must be at least 1%s");
-    if ((long long)n * K >= (1LL << 40)) return fail(OFMK_E_ARG, "n * K must be < 2^40%s");
+    if (int rc = check_search_args(opts, n, h, w, H, W, in && cands && scores, K)) return rc;
     SvdArgs sa;
     if (int rc = check_resync_scales(sa, scales, blk, true)) return rc;
     const Ctx cx = make_ctx(stream, opts);
@@ -1893,16 +1909,11 @@ int ofmk_svd_affine_scores_rgb8(const uint8_t *in, int n, int h, int w, int H, i
     a.scale = sa.scales[1];
     const long long tiles = (long long)a.tiles_x * ((a.rows + kAffineTile - 1) / kAffineTile);
     const AffineMap *dc = reinterpret_cast<const AffineMap *>(cands);
-    for_chunks(K, kMaxChunk, [&](int k0, int ck) {
-        const long long room = (1LL << 30) / (tiles * ck);                       // workgroups per launch stay below 2^30
-        const int cap = room < 1 ? 1 : room > kMaxChunk ? kMaxChunk : (int)room;
-        return for_chunks(n, cap, [&](int f0, int cf) {
-            ScopedTiming timing(KIND_SVD, cx);
-            OFMK_TIMED_LAUNCH(timing, svd_affine_scores_rgb8_kernel, dim3((unsigned)tiles, (unsigned)ck, (unsigned)cf), dim3(kThreads), 0, cx.s,
-                              in + (size_t)f0 * a.frame_stride, dc + k0, a,
-                              reinterpret_cast<unsigned long long *>(scores) + (size_t)f0 * K + k0);
-            return OFMK_OK;
-        });
+    for_cand_frame_chunks(tiles, K, n, [&](int k0, int ck, int f0, int cf) {
+        ScopedTiming timing(KIND_SVD, cx);
+        OFMK_TIMED_LAUNCH(timing, svd_affine_scores_rgb8_kernel, dim3((unsigned)tiles, (unsigned)ck, (unsigned)cf), dim3(kThreads), 0, cx.s,
+                          in + (size_t)f0 * a.frame_stride, dc + k0, a, reinterpret_cast<unsigned long long *>(scores) + (size_t)f0 * K + k0);
+        return OFMK_OK;
     });
     HIP_TRY(hipGetLastError());
     return OFMK_OK;
@@ -1913,12 +1924,7 @@ int ofmk_svd_affine_scores_rgb8(const uint8_t *in, int n, int h, int w, int H, i
 // by the launches that hold the call's first frame only.  Both are cleared here whatever they held.  Chunks as above.
 int ofmk_svd_affine_phase_scores_rgb8(const uint8_t *in, int n, int h, int w, int H, int W, const ofmk_affine *cands, int K, const double *scales,
                                       int blk, long long *scores, long long *units, void *stream, const ofmk_opts *opts) {
-    if (int orc = check_opts(opts)) return orc;
-    if (int rc = check_dims(n, H, W)) return rc;
-    if (int rc = check_leak_dims(h, w)) return rc;
-    if (!in || !cands || !scores) return fail(OFMK_E_ARG, "null pointer%s");
-    if (K < 1) return fail(OFMK_E_ARG, "K must be at least 1%s");
-    if ((long long)n * K >= (1LL << 40)) return fail(OFMK_E_ARG, "n * K must be < 2^40%s");
+    if (int rc = check_search_args(opts, n, h, w, H, W, in && cands && scores, K)) return rc;
     SvdArgs sa;
     if (int rc = check_resync_scales(sa, scales, blk, true)) return rc;
     const Ctx cx = make_ctx(stream, opts);
@@ -1935,18 +1941,14 @@ int ofmk_svd_affine_phase_scores_rgb8(const uint8_t *in, int n, int h, int w, in
     const long long rects = (long long)a.rects_x * ((a.oh + kPhaseRect - 1) / kPhaseRect);
     const AffineMap *dc = reinterpret_cast<const AffineMap *>(cands);
     unsigned long long *du = reinterpret_cast<unsigned long long *>(units);
-    for_chunks(K, kMaxChunk, [&](int k0, int ck) {
-        const long long room = (1LL << 30) / (rects * ck);                       // workgroups per launch stay below 2^30
-        const int cap = room < 1 ? 1 : room > kMaxChunk ? kMaxChunk : (int)room;
-        return for_chunks(n, cap, [&](int f0, int cf) {
-            ScopedTiming timing(KIND_SVD, cx);
-            AffinePhaseArgs ac = a;
-            ac.count_units = units && f0 == 0;                                   // once per call: the chunk with the first frame
-            OFMK_TIMED_LAUNCH(timing, svd_affine_phase_scores_rgb8_kernel, dim3((unsigned)rects, (unsigned)ck, (unsigned)cf), dim3(kThreads), 0, cx.s,
-                              in + (size_t)f0 * a.frame_stride, dc + k0, ac,
-                              reinterpret_cast<unsigned long long *>(scores) + ((size_t)f0 * K + k0) * 64, units ? du + (size_t)k0 * 64 : du);
-            return OFMK_OK;
-        });
+    for_cand_frame_chunks(rects, K, n, [&](int k0, int ck, int f0, int cf) {
+        ScopedTiming timing(KIND_SVD, cx);
+        AffinePhaseArgs ac = a;
+        ac.count_units = units && f0 == 0;                                       // once per call: the chunk with the first frame
+        OFMK_TIMED_LAUNCH(timing, svd_affine_phase_scores_rgb8_kernel, dim3((unsigned)rects, (unsigned)ck, (unsigned)cf), dim3(kThreads), 0, cx.s,
+                          in + (size_t)f0 * a.frame_stride, dc + k0, ac,
+                          reinterpret_cast<unsigned long long *>(scores) + ((size_t)f0 * K + k0) * 64, units ? du + (size_t)k0 * 64 : du);
+        return OFMK_OK;
     });
     HIP_TRY(hipGetLastError());
     return OFMK_OK;
@@ -1956,37 +1958,7 @@ int ofmk_svd_affine_phase_scores_rgb8(const uint8_t *in, int n, int h, int w, in
 // int64 [n][L], cleared here.  scales[1] <= 0 or no counting unit: all zeros.
 int ofmk_svd_detect_soft_affine_rgb8(const uint8_t *in, int n, int h, int w, int H, int W, const ofmk_affine *geom, int L, const double *scales,
                                      int blk, long long *soft, void *stream, const ofmk_opts *opts) {
-    if (int orc = check_opts(opts)) return orc;
-    if (int rc = check_soft_args(in, n, H, W, L, soft)) return rc;
-    if (int rc = check_leak_dims(h, w)) return rc;
-    if (!geom) return fail(OFMK_E_ARG, "null pointer%s");
-    AffineReadArgs a;
-    if (int rc = check_affine_map(geom, a.m)) return rc;
-    SvdArgs sa;
-    if (int rc = check_resync_scales(sa, scales, blk, false)) return rc;
-    const Ctx cx = make_ctx(stream, opts);
-    HIP_TRY(launch_zero(soft, (size_t)n * L * sizeof(long long), cx.s));
-    int r[5];
-    affine_rect(a.m, h, w, H, W, r);
-    if (!(sa.scales[1] > 0.f) || r[4] == 0) return OFMK_OK;
-    a.h = h; a.w = w;
-    a.i0 = r[0]; a.j0 = r[2];
-    a.cols = r[3] - r[2];
-    a.nunits = (r[1] - r[0]) * a.cols;
-    a.canvas_cols = W / 8;
-    a.L = L;
-    a.frame_stride = (size_t)h * w * 3;
-    a.scale = sa.scales[1];
-    for_chunks(n, kMaxChunk, [&](int f0, int cf) {
-        ScopedTiming timing(KIND_SVD, cx);
-        AffineReadArgs ac = a;
-        ac.frames = cf;
-        ac.soft = soft + (size_t)f0 * L;
-        OFMK_TIMED_LAUNCH(timing, svd_soft_affine_rgb8_kernel, xcd_grid(a.nunits, cf), dim3(kThreads), 0, cx.s, in + (size_t)f0 * a.frame_stride, ac);
-        return OFMK_OK;
-    });
-    HIP_TRY(hipGetLastError());
-    return OFMK_OK;
+    return svd_detect_soft_mapped<AffineReadArgs, svd_soft_affine_rgb8_kernel>(in, n, h, w, H, W, geom, L, scales, blk, soft, stream, opts);
 }
 
 // ---- leaks read against their source frames (align_kernels.hiph; build extensions, not reference semantics) ----------------------
@@ -1994,13 +1966,7 @@ int ofmk_svd_detect_soft_affine_rgb8(const uint8_t *in, int n, int h, int w, int
 // [n][K][29], cleared here whatever it held; an out-of-range candidate leaves 29 zeros.  Chunks as ofmk_svd_affine_scores_rgb8.
 int ofmk_align_sums_rgb8(const uint8_t *src, const uint8_t *leak, int n, int h, int w, int H, int W, const ofmk_affine *cands, int K,
                          long long *sums, void *stream, const ofmk_opts *opts) {
-    if (int orc = check_opts(opts)) return orc;
-    if (int rc = check_dims(n, H, W)) return rc;
-    if (H > kAlignMaxSide || W > kAlignMaxSide) return fail(OFMK_E_ARG, "canvas H, W must be at most 4096 (the sums are int64)%s");
-    if (int rc = check_leak_dims(h, w)) return rc;
-    if (!src || !leak || !cands || !sums) return fail(OFMK_E_ARG, "null pointer%s");
-    if (K < 1) return fail(OFMK_E_ARG, "K must be at least 1%s");
-    if ((long long)n * K >= (1LL << 40)) return fail(OFMK_E_ARG, "n * K must be < 2^40%s");
+    if (int rc = check_search_args(opts, n, h, w, H, W, src && leak && cands && sums, K, kAlignMaxSide, " (the sums are int64)")) return rc;
     const Ctx cx = make_ctx(stream, opts);
     HIP_TRY(launch_zero(sums, (size_t)n * K * kAlignSums * sizeof(long long), cx.s));
     AlignArgs a;
@@ -2011,16 +1977,12 @@ int ofmk_align_sums_rgb8(const uint8_t *src, const uint8_t *leak, int n, int h, 
     a.src_stride = (size_t)H * W * 3;
     const long long tiles = (long long)a.tiles_x * ((H + kAlignTile - 1) / kAlignTile);
     const AffineMap *dc = reinterpret_cast<const AffineMap *>(cands);
-    for_chunks(K, kMaxChunk, [&](int k0, int ck) {
-        const long long room = (1LL << 30) / (tiles * ck);                       // workgroups per launch stay below 2^30
-        const int cap = room < 1 ? 1 : room > kMaxChunk ? kMaxChunk : (int)room;
-        return for_chunks(n, cap, [&](int f0, int cf) {
-            ScopedTiming timing(KIND_SVD, cx);
-            OFMK_TIMED_LAUNCH(timing, align_sums_rgb8_kernel, dim3((unsigned)tiles, (unsigned)ck, (unsigned)cf), dim3(kThreads), 0, cx.s,
-                              src + (size_t)f0 * a.src_stride, leak + (size_t)f0 * a.leak_stride, dc + k0, a,
-                              reinterpret_cast<unsigned long long *>(sums) + ((size_t)f0 * K + k0) * kAlignSums);
-            return OFMK_OK;
-        });
+    for_cand_frame_chunks(tiles, K, n, [&](int k0, int ck, int f0, int cf) {
+        ScopedTiming timing(KIND_SVD, cx);
+        OFMK_TIMED_LAUNCH(timing, align_sums_rgb8_kernel, dim3((unsigned)tiles, (unsigned)ck, (unsigned)cf), dim3(kThreads), 0, cx.s,
+                          src + (size_t)f0 * a.src_stride, leak + (size_t)f0 * a.leak_stride, dc + k0, a,
+                          reinterpret_cast<unsigned long long *>(sums) + ((size_t)f0 * K + k0) * kAlignSums);
+        return OFMK_OK;
     });
     HIP_TRY(hipGetLastError());
     return OFMK_OK;
@@ -2092,7 +2054,7 @@ int ofmk_align_residuals_rgb8(const uint8_t *lib, int N, const uint8_t *leak, in
     if (span < 1 || span > kResidualMaxSpan) return fail(OFMK_E_ARG, "span must be in [1, 16]%s");
     if (!lib || !leak || !first || !geom || !res) return fail(OFMK_E_ARG, "null pointer%s");
     ResidualArgs a;
-    if (int rc = check_affine_map(geom, a.m)) return rc;
+    if (int rc = check_map(geom, a.m)) return rc;
     const Ctx cx = make_ctx(stream, opts);
     HIP_TRY(launch_zero(res, (size_t)m * span * 2 * sizeof(long long), cx.s));
     a.h = h; a.w = w; a.H = H; a.W = W;
@@ -2140,13 +2102,7 @@ int ofmk_histograms_rgb8(const uint8_t *in, int n, int h, int w, long long *hist
 // candidate leaves zeros.  Chunks as ofmk_align_sums_rgb8.
 int ofmk_tone_sums_rgb8(const uint8_t *src, const uint8_t *leak, int n, int h, int w, int H, int W, const ofmk_affine *cands, int K,
                         long long *sums, void *stream, const ofmk_opts *opts) {
-    if (int orc = check_opts(opts)) return orc;
-    if (int rc = check_dims(n, H, W)) return rc;
-    if (H > kAlignMaxSide || W > kAlignMaxSide) return fail(OFMK_E_ARG, "canvas H, W must be at most 4096%s");
-    if (int rc = check_leak_dims(h, w)) return rc;
-    if (!src || !leak || !cands || !sums) return fail(OFMK_E_ARG, "null pointer%s");
-    if (K < 1) return fail(OFMK_E_ARG, "K must be at least 1%s");
-    if ((long long)n * K >= (1LL << 40)) return fail(OFMK_E_ARG, "n * K must be < 2^40%s");
+    if (int rc = check_search_args(opts, n, h, w, H, W, src && leak && cands && sums, K, kAlignMaxSide)) return rc;
     const Ctx cx = make_ctx(stream, opts);
     HIP_TRY(launch_zero(sums, (size_t)n * K * kToneWords * sizeof(long long), cx.s));
     ToneSumsArgs a;
@@ -2157,16 +2113,12 @@ int ofmk_tone_sums_rgb8(const uint8_t *src, const uint8_t *leak, int n, int h, i
     a.src_stride = (size_t)H * W * 3;
     const long long tiles = (long long)a.tiles_x * ((H + kAlignTile - 1) / kAlignTile);
     const AffineMap *dc = reinterpret_cast<const AffineMap *>(cands);
-    for_chunks(K, kMaxChunk, [&](int k0, int ck) {
-        const long long room = (1LL << 30) / (tiles * ck);                       // workgroups per launch stay below 2^30
-        const int cap = room < 1 ? 1 : room > kMaxChunk ? kMaxChunk : (int)room;
-        return for_chunks(n, cap, [&](int f0, int cf) {
-            ScopedTiming timing(KIND_SVD, cx);
-            OFMK_TIMED_LAUNCH(timing, tone_sums_rgb8_kernel, dim3((unsigned)tiles, (unsigned)ck, (unsigned)cf), dim3(kThreads), 0, cx.s,
-                              src + (size_t)f0 * a.src_stride, leak + (size_t)f0 * a.leak_stride, dc + k0, a,
-                              reinterpret_cast<unsigned long long *>(sums) + ((size_t)f0 * K + k0) * kToneWords);
-            return OFMK_OK;
-        });
+    for_cand_frame_chunks(tiles, K, n, [&](int k0, int ck, int f0, int cf) {
+        ScopedTiming timing(KIND_SVD, cx);
+        OFMK_TIMED_LAUNCH(timing, tone_sums_rgb8_kernel, dim3((unsigned)tiles, (unsigned)ck, (unsigned)cf), dim3(kThreads), 0, cx.s,
+                          src + (size_t)f0 * a.src_stride, leak + (size_t)f0 * a.leak_stride, dc + k0, a,
+                          reinterpret_cast<unsigned long long *>(sums) + ((size_t)f0 * K + k0) * kToneWords);
+        return OFMK_OK;
     });
     HIP_TRY(hipGetLastError());
     return OFMK_OK;

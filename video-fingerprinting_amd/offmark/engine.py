@@ -238,6 +238,20 @@ class DctEngine:
         shape = (n, L) if copies is None else (copies, n, L)
         return self._buffer("soft", None if soft is True else soft, shape, self.torch.int64, self.device)
 
+    def _on_device(self, x, dtype):
+        """A small input of a call (``dtype``: the name numpy and torch share): the tensor on this device, or an array copied there."""
+        t = self.torch
+        if not isinstance(x, t.Tensor):
+            x = t.from_numpy(np.ascontiguousarray(np.asarray(x, dtype=dtype)))
+        return x.to(device=self.device, dtype=getattr(t, dtype)).contiguous()
+
+    def _cands(self, cands, cols):
+        """The candidate list of a search call -> (int64 [K, cols] on this device, K)."""
+        cands = self._on_device(cands, "int64")
+        if cands.dim() != 2 or cands.shape[1] != cols or cands.shape[0] < 1:
+            raise ValueError(f"cands must be int64 [K, {cols}] with K >= 1")
+        return cands, int(cands.shape[0])
+
     def _layout(self, layout):
         try:
             return self._LAYOUT[layout]
@@ -655,12 +669,7 @@ class DctEngine:
         device or an array (copied there).  No warped frame is written.  offmark.resync.best_geometry reads the result."""
         t = self.torch
         n, h, w = self._check_frames(frames, t.uint8)
-        if not isinstance(cands, t.Tensor):
-            cands = t.from_numpy(np.ascontiguousarray(np.asarray(cands, dtype=np.int64)))
-        cands = cands.to(device=self.device, dtype=t.int64).contiguous()
-        if cands.dim() != 2 or cands.shape[1] != 4 or cands.shape[0] < 1:
-            raise ValueError("cands must be int64 [K, 4] with K >= 1")
-        K = int(cands.shape[0])
+        cands, K = self._cands(cands, 4)
         scores = self._soft(scores, n, K)
         _hip.check(self.lib.ofmk_svd_warp_scores_rgb8(frames.data_ptr(), n, h, w, int(canvas_hw[0]), int(canvas_hw[1]), cands.data_ptr(), K,
                                                       _hip.scales3(scale, scales), int(blk), scores.data_ptr(), _hip.current_stream(),
@@ -713,12 +722,7 @@ class DctEngine:
         device or an array (copied there).  int64 [n, K]; a candidate out of range or without a counting unit scores 0."""
         t = self.torch
         n, h, w = self._check_frames(frames, t.uint8)
-        if not isinstance(cands, t.Tensor):
-            cands = t.from_numpy(np.ascontiguousarray(np.asarray(cands, dtype=np.int64)))
-        cands = cands.to(device=self.device, dtype=t.int64).contiguous()
-        if cands.dim() != 2 or cands.shape[1] != 6 or cands.shape[0] < 1:
-            raise ValueError("cands must be int64 [K, 6] with K >= 1")
-        K = int(cands.shape[0])
+        cands, K = self._cands(cands, 6)
         scores = self._soft(scores, n, K)
         _hip.check(self.lib.ofmk_svd_affine_scores_rgb8(frames.data_ptr(), n, h, w, int(canvas_hw[0]), int(canvas_hw[1]), cands.data_ptr(), K,
                                                         _hip.scales3(scale, scales), int(blk), scores.data_ptr(), _hip.current_stream(),
@@ -733,12 +737,7 @@ class DctEngine:
         (None is returned for them).  offmark.resync.best_shifted_geometry reads the result."""
         t = self.torch
         n, h, w = self._check_frames(frames, t.uint8)
-        if not isinstance(cands, t.Tensor):
-            cands = t.from_numpy(np.ascontiguousarray(np.asarray(cands, dtype=np.int64)))
-        cands = cands.to(device=self.device, dtype=t.int64).contiguous()
-        if cands.dim() != 2 or cands.shape[1] != 6 or cands.shape[0] < 1:
-            raise ValueError("cands must be int64 [K, 6] with K >= 1")
-        K = int(cands.shape[0])
+        cands, K = self._cands(cands, 6)
         scores = self._soft(scores, K, 64, copies=n)
         units = None if units is False else self._soft(units, K, 64)
         _hip.check(self.lib.ofmk_svd_affine_phase_scores_rgb8(frames.data_ptr(), n, h, w, int(canvas_hw[0]), int(canvas_hw[1]), cands.data_ptr(),
@@ -769,12 +768,7 @@ class DctEngine:
         m, h, w = self._check_frames(frames, t.uint8)
         if m != n:
             raise ValueError("one source frame per leak frame")
-        if not isinstance(cands, t.Tensor):
-            cands = t.from_numpy(np.ascontiguousarray(np.asarray(cands, dtype=np.int64)))
-        cands = cands.to(device=self.device, dtype=t.int64).contiguous()
-        if cands.dim() != 2 or cands.shape[1] != 6 or cands.shape[0] < 1:
-            raise ValueError("cands must be int64 [K, 6] with K >= 1")
-        K = int(cands.shape[0])
+        cands, K = self._cands(cands, 6)
         sums = self._soft(sums, K, 29, copies=n)
         _hip.check(self.lib.ofmk_align_sums_rgb8(sources.data_ptr(), frames.data_ptr(), n, h, w, H, W, cands.data_ptr(), K, sums.data_ptr(),
                                                  _hip.current_stream(), self._o()))
@@ -824,9 +818,7 @@ class DctEngine:
         t = self.torch
         N, H, W = self._check_frames(library, t.uint8)
         m, h, w = self._check_frames(frames, t.uint8)
-        if not isinstance(first, t.Tensor):
-            first = t.from_numpy(np.ascontiguousarray(np.asarray(first, dtype=np.int32)))
-        first = first.to(device=self.device, dtype=t.int32).contiguous()
+        first = self._on_device(first, "int32")
         if first.dim() != 1 or first.shape[0] != m:
             raise ValueError("first must be int32 [m], one entry per leak frame")
         span = int(span)
@@ -859,12 +851,7 @@ class DctEngine:
         m, h, w = self._check_frames(frames, t.uint8)
         if m != n:
             raise ValueError("one source frame per leak frame")
-        if not isinstance(cands, t.Tensor):
-            cands = t.from_numpy(np.ascontiguousarray(np.asarray(cands, dtype=np.int64)))
-        cands = cands.to(device=self.device, dtype=t.int64).contiguous()
-        if cands.dim() != 2 or cands.shape[1] != 6 or cands.shape[0] < 1:
-            raise ValueError("cands must be int64 [K, 6] with K >= 1")
-        K = int(cands.shape[0])
+        cands, K = self._cands(cands, 6)
         sums = self._buffer("sums", sums, (n, K, 3, 256, 2), t.int64, self.device)
         _hip.check(self.lib.ofmk_tone_sums_rgb8(sources.data_ptr(), frames.data_ptr(), n, h, w, H, W, cands.data_ptr(), K, sums.data_ptr(),
                                                 _hip.current_stream(), self._o()))
@@ -875,9 +862,7 @@ class DctEngine:
         this device or an array (copied there); ``out`` may be ``frames`` itself (ofmk_apply_tone_rgb8)."""
         t = self.torch
         n, h, w = self._check_frames(frames, t.uint8)
-        if not isinstance(lut, t.Tensor):
-            lut = t.from_numpy(np.ascontiguousarray(np.asarray(lut, dtype=np.uint8)))
-        lut = lut.to(device=self.device, dtype=t.uint8).contiguous()
+        lut = self._on_device(lut, "uint8")
         if tuple(lut.shape) != (3, 256):
             raise ValueError("lut must be uint8 [3, 256]")
         out = self._out(out, frames)
