@@ -707,6 +707,33 @@ int ofmk_signature_distances(const uint8_t *a, int m, const uint8_t *b, int N, i
 int ofmk_align_residuals_rgb8(const uint8_t *lib, int N, const uint8_t *leak, int m, int h, int w, int H, int W, const int32_t *first,
                               int span, const ofmk_affine *geom, long long *res, void *stream, const ofmk_opts *opts);
 
+/* ---- a leaked clip whose TONE changed as well: tone-invariant frame matching (BUILD EXTENSION) -----------------------------------
+ * A re-graded or screen-captured clip is both a clip (above) and a leak whose values changed (below).  In a dissolve brightness is
+ * time, so the plain signature loses its strongest cue, and sum e*e moves more with a gain than with a wrong frame.  Two calls make
+ * the two passes of offmark.temporal tone invariant (offmark.temporal.read_toned_leak_clip); all integers, equal to the NumPy
+ * statement (tests/_toned_clip.py).
+ *
+ * ofmk_align_moments_rgb8: the arguments of ofmk_align_residuals_rgb8, their rules and its OFMK_E_ARG cases; mom is device int64
+ *   [m][span][6], cleared by the call whatever it held.  With l the warped luma of leak frame i under geom, s the luma of
+ *   lib[first[i] + j] and the sums over ofmk_align_sums_rgb8's contributing pixels (interior canvas pixels inside the leak):
+ *       mom[i][j] = (count, sum l, sum s, sum l*l, sum s*s, sum l*s)
+ *   A source index outside 0..N-1 leaves six zeros; the list is not read on the host.  mom[3] + mom[4] - 2*mom[5] equals
+ *   ofmk_align_residuals_rgb8's sum e*e and mom[0] its count, integer for integer.  The zero-mean normalised cross-correlation they
+ *   give (offmark.temporal.ncc_cost) does not see a gain or an offset on either side.  ofmk_align_residuals_rgb8's workgroup: a tile of
+ *   64 x 64 canvas pixels of one leak frame, the warped luma formed once and kept in registers, then the span sources, reading only
+ *   their luma; per source three sums reduced in 32 bits (a tile's sum s*s, sum l*l, sum l*s stay below 4096 * 255^2 < 2^29, sum l
+ *   and sum s below 2^20): wavefront, LDS, then at most 6*span 64-bit atomics per workgroup -- integer adds, so the order is free.
+ *   No warped frame and no gathered source is written.  Leak frames in gridDim.y, chunked at 65535.
+ * ofmk_signature_ranks: sig is device u8 [n][64] (ofmk_signature_rgb8's); rank is device u8 [n][64], every byte written:
+ *       rank[f][c] = the number of c' < 64 with (sig[f][c'], c') < (sig[f][c], c)     (pairs compared in order: value, then index)
+ *   a permutation of 0..63 per frame, which any increasing tone curve leaves unchanged; ofmk_signature_distances runs on ranks as it
+ *   does on signatures (at most 2048).  One wavefront per frame, a lane per cell, the 64 keys read lane by lane; no LDS.
+ *   Required, else OFMK_E_ARG: n >= 1, no null pointer.
+ * Both calls allocate nothing, synchronise nothing and are graph capturable; both are timed as kind 4 (svd); the flags are ignored. */
+int ofmk_align_moments_rgb8(const uint8_t *lib, int N, const uint8_t *leak, int m, int h, int w, int H, int W, const int32_t *first,
+                            int span, const ofmk_affine *geom, long long *mom, void *stream, const ofmk_opts *opts);
+int ofmk_signature_ranks(const uint8_t *sig, int n, uint8_t *rank, void *stream, const ofmk_opts *opts);
+
 /* ---- reading a leak whose VALUES changed: a tone curve fitted against the SOURCE frames (BUILD EXTENSION) ----------------------
  * A screen capture, a re-grade or a range mix-up changes a leak's brightness, contrast or gamma, and the DwtDctSvd mark -- the place
  * of a singular value inside a cell 15 wide -- does not survive a gain of a few percent.  The operator holds the source frames, so the

@@ -1661,6 +1661,36 @@ int soft_window(const LeakFmt &f, const uint8_t *in, int n, int py, int px, int 
     });
 }
 
+// The residuals and the moments share arguments, checks, tiles and chunks; WORDS int64 per leak frame and source, cleared here.
+template <auto Kernel, int WORDS>
+int align_window_sums(const uint8_t *lib, int N, const uint8_t *leak, int m, int h, int w, int H, int W, const int32_t *first, int span,
+                             const ofmk_affine *geom, long long *res, void *stream, const ofmk_opts *opts) {
+    if (int orc = check_opts(opts)) return orc;
+    if (int rc = check_dims(m, H, W)) return rc;
+    if (N < 1) return fail(OFMK_E_ARG, "N must be at least 1%s");
+    if (H > kAlignMaxSide || W > kAlignMaxSide) return fail(OFMK_E_ARG, "canvas H, W must be at most 4096%s");
+    if (int rc = check_leak_dims(h, w)) return rc;
+    if (span < 1 || span > kResidualMaxSpan) return fail(OFMK_E_ARG, "span must be in [1, 16]%s");
+    if (!lib || !leak || !first || !geom || !res) return fail(OFMK_E_ARG, "null pointer%s");
+    ResidualArgs a;
+    if (int rc = check_map(geom, a.m)) return rc;
+    const Ctx cx = make_ctx(stream, opts);
+    HIP_TRY(launch_zero(res, (size_t)m * span * WORDS * sizeof(long long), cx.s));
+    a.h = h; a.w = w; a.H = H; a.W = W;
+    a.tiles_x = (W + kAlignTile - 1) / kAlignTile;
+    a.N = N; a.span = span;
+    a.leak_stride = (size_t)h * w * 3;
+    a.src_stride = (size_t)H * W * 3;
+    const int tiles = a.tiles_x * ((H + kAlignTile - 1) / kAlignTile);          // at most 64 * 64
+    for_chunks(m, kMaxChunk, [&](int f0, int cf) {
+        ScopedTiming timing(KIND_SVD, cx);
+        OFMK_TIMED_LAUNCH(timing, Kernel, dim3((unsigned)tiles, (unsigned)cf), dim3(kThreads), 0, cx.s, lib,
+                          leak + (size_t)f0 * a.leak_stride, first + f0, a, reinterpret_cast<unsigned long long *>(res) + (size_t)f0 * span * WORDS);
+        return OFMK_OK;
+    });
+    HIP_TRY(hipGetLastError());
+    return OFMK_OK;
+}
 
 }  // namespace
 
@@ -2046,29 +2076,26 @@ int ofmk_signature_distances(const uint8_t *a, int m, const uint8_t *b, int N, i
 // a source index outside 0..N-1 leaves (0, 0).
 int ofmk_align_residuals_rgb8(const uint8_t *lib, int N, const uint8_t *leak, int m, int h, int w, int H, int W, const int32_t *first, int span,
                               const ofmk_affine *geom, long long *res, void *stream, const ofmk_opts *opts) {
+    return align_window_sums<align_residuals_rgb8_kernel, 2>(lib, N, leak, m, h, w, H, W, first, span, geom, res, stream, opts);
+}
+
+// mom[i][j] = (n, sum l, sum s, sum l^2, sum s^2, sum l s) over ofmk_align_residuals_rgb8's contributing pixels, l the luma of leak frame
+// i warped by *geom (HOST memory), s the luma of lib[first[i] + j]; int64 [m][span][6], cleared here whatever it held; the arguments and
+// their rules are ofmk_align_residuals_rgb8's, and mom[3] + mom[4] - 2 mom[5] is its sum e^2, mom[0] its count.
+int ofmk_align_moments_rgb8(const uint8_t *lib, int N, const uint8_t *leak, int m, int h, int w, int H, int W, const int32_t *first, int span,
+                            const ofmk_affine *geom, long long *mom, void *stream, const ofmk_opts *opts) {
+    return align_window_sums<align_moments_rgb8_kernel, kMomentSums>(lib, N, leak, m, h, w, H, W, first, span, geom, mom, stream, opts);
+}
+
+// rank[f][c] = the number of cells c' of signature f with (sig[f][c'], c') < (sig[f][c], c); u8 [n][64], every byte written.
+int ofmk_signature_ranks(const uint8_t *sig, int n, uint8_t *rank, void *stream, const ofmk_opts *opts) {
     if (int orc = check_opts(opts)) return orc;
-    if (int rc = check_dims(m, H, W)) return rc;
-    if (N < 1) return fail(OFMK_E_ARG, "N must be at least 1%s");
-    if (H > kAlignMaxSide || W > kAlignMaxSide) return fail(OFMK_E_ARG, "canvas H, W must be at most 4096%s");
-    if (int rc = check_leak_dims(h, w)) return rc;
-    if (span < 1 || span > kResidualMaxSpan) return fail(OFMK_E_ARG, "span must be in [1, 16]%s");
-    if (!lib || !leak || !first || !geom || !res) return fail(OFMK_E_ARG, "null pointer%s");
-    ResidualArgs a;
-    if (int rc = check_map(geom, a.m)) return rc;
+    if (n < 1) return fail(OFMK_E_ARG, "n must be at least 1%s");
+    if (!sig || !rank) return fail(OFMK_E_ARG, "null pointer%s");
     const Ctx cx = make_ctx(stream, opts);
-    HIP_TRY(launch_zero(res, (size_t)m * span * 2 * sizeof(long long), cx.s));
-    a.h = h; a.w = w; a.H = H; a.W = W;
-    a.tiles_x = (W + kAlignTile - 1) / kAlignTile;
-    a.N = N; a.span = span;
-    a.leak_stride = (size_t)h * w * 3;
-    a.src_stride = (size_t)H * W * 3;
-    const int tiles = a.tiles_x * ((H + kAlignTile - 1) / kAlignTile);          // at most 64 * 64
-    for_chunks(m, kMaxChunk, [&](int f0, int cf) {
-        ScopedTiming timing(KIND_SVD, cx);
-        OFMK_TIMED_LAUNCH(timing, align_residuals_rgb8_kernel, dim3((unsigned)tiles, (unsigned)cf), dim3(kThreads), 0, cx.s, lib,
-                          leak + (size_t)f0 * a.leak_stride, first + f0, a, reinterpret_cast<unsigned long long *>(res) + (size_t)f0 * span * 2);
-        return OFMK_OK;
-    });
+    ScopedTiming timing(KIND_SVD, cx);
+    OFMK_TIMED_LAUNCH(timing, signature_ranks_kernel, dim3((unsigned)(((long long)n + kThreads / 64 - 1) / (kThreads / 64))), dim3(kThreads), 0, cx.s,
+                      sig, n, rank);
     HIP_TRY(hipGetLastError());
     return OFMK_OK;
 }

@@ -132,7 +132,9 @@ SIGNATURES = {
     "ofmk_signature_rgb8": (_i32, [_vp, _i32, _i32, _i32, _vp, _vp, _op]),
     "ofmk_signature_distances": (_i32, [_vp, _i32, _vp, _i32, _vp, _vp, _op]),
     "ofmk_align_residuals_rgb8": (_i32, [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _ap, _vp, _vp, _op]),
-    "ofmk_histograms_rgb8": (_i32, [_vp, _i32, _i32, _i32, _vp, _vp, _op]),
+    "ofmk_align_moments_rgb8": (_i32, [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _ap, _vp, _vp, _op]),
+    "ofmk_signature_ranks": (_i32, [_vp, _i32, _vp, _vp, _op]),
+    "ofmk_histograms_rgb8":(_i32, [_vp, _i32, _i32, _i32, _vp, _vp, _op]),
     "ofmk_tone_sums_rgb8": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _op]),
     "ofmk_apply_tone_rgb8": (_i32, [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _op]),
     "ofmk_probe_xcc":(_i32, [_vp, _i32, _vp, _op]),

@@ -809,12 +809,8 @@ class DctEngine:
         _hip.check(self.lib.ofmk_signature_distances(a.data_ptr(), m, b.data_ptr(), N, out.data_ptr(), _hip.current_stream(), self._o()))
         return out
 
-    def align_residuals(self, library, frames, first, span, geom, out=None):
-        """The luma residual of every leak frame against a window of source frames under ONE geometry: library uint8 [N, H, W, 3],
-        H, W <= 4096; frames uint8 [m, h, w, 3]; ``first``: int32 [m], a tensor on this device or an array (copied there); span in
-        1..16 -> int64 [m, span, 2]: entry j of frame i is (sum e^2, contributing pixels) against library[first[i] + j], exactly
-        align_sums' [27] and [28] of that pair; (0, 0) where the index leaves the library (ofmk_align_residuals_rgb8).  No warped frame
-        and no gathered source is written."""
+    def _window_sums(self, call, words, library, frames, first, span, geom, out):
+        """align_residuals / align_moments: int64 [m, span, words] of every leak frame against library[first[i] + j], j < span."""
         t = self.torch
         N, H, W = self._check_frames(library, t.uint8)
         m, h, w = self._check_frames(frames, t.uint8)
@@ -824,10 +820,33 @@ class DctEngine:
         span = int(span)
         if not 1 <= span <= 16:
             raise ValueError("span must be in 1..16")
-        out = self._soft(out, span, 2, copies=m)
+        out = self._soft(out, span, words, copies=m)
         g = self._affine_geom(geom)
-        _hip.check(self.lib.ofmk_align_residuals_rgb8(library.data_ptr(), N, frames.data_ptr(), m, h, w, H, W, first.data_ptr(), span, C.byref(g),
-                                                      out.data_ptr(), _hip.current_stream(), self._o()))
+        _hip.check(call(library.data_ptr(), N, frames.data_ptr(), m, h, w, H, W, first.data_ptr(), span, C.byref(g), out.data_ptr(),
+                        _hip.current_stream(), self._o()))
+        return out
+
+    def align_residuals(self, library, frames, first, span, geom, out=None):
+        """The luma residual of every leak frame against a window of source frames under ONE geometry: library uint8 [N, H, W, 3],
+        H, W <= 4096; frames uint8 [m, h, w, 3]; ``first``: int32 [m], a tensor on this device or an array (copied there); span in
+        1..16 -> int64 [m, span, 2]: entry j of frame i is (sum e^2, contributing pixels) against library[first[i] + j], exactly
+        align_sums' [27] and [28] of that pair; (0, 0) where the index leaves the library (ofmk_align_residuals_rgb8).  No warped frame
+        and no gathered source is written."""
+        return self._window_sums(self.lib.ofmk_align_residuals_rgb8, 2, library, frames, first, span, geom, out)
+
+    # -- a leaked clip whose tone changed as well (build extension; offmark.temporal.read_toned_leak_clip) ----------------------------
+    def align_moments(self, library, frames, first, span, geom, out=None):
+        """align_residuals' arguments -> int64 [m, span, 6]: entry j of frame i is (count, sum l, sum s, sum l^2, sum s^2, sum l s)
+        over align_residuals' contributing pixels, l the warped luma of leak frame i, s the luma of library[first[i] + j]; six zeros
+        where the index leaves the library (ofmk_align_moments_rgb8).  [3] + [4] - 2 [5] is align_residuals' sum e^2, [0] its count."""
+        return self._window_sums(self.lib.ofmk_align_moments_rgb8, 6, library, frames, first, span, geom, out)
+
+    def signature_ranks(self, sig, out=None):
+        """The rank signature: uint8 [n, 64] -> uint8 [n, 64], rank[f, c] = #{c' : (sig[f, c'], c') < (sig[f, c], c)}, a permutation
+        of 0..63 that an increasing tone curve leaves unchanged (ofmk_signature_ranks)."""
+        n = self._signature_list("sig", sig)
+        out = self._buffer("out", out, (n, 64), self.torch.uint8, self.device)
+        _hip.check(self.lib.ofmk_signature_ranks(sig.data_ptr(), n, out.data_ptr(), _hip.current_stream(), self._o()))
         return out
 
     # -- leaks whose values changed: a tone curve fitted against the source frames (build extension; offmark.tone) ---------------------

@@ -115,6 +115,18 @@ class DwtDctSvdDecoder:
             raise ValueError("the library frames must have the canvas's size")
         return self.engine.align_residuals(library, frames, first, span, geom)
 
+    # -- a leaked clip whose tone changed as well (build extension: offmark.temporal.read_toned_leak_clip) ------------------------------
+    def signature_ranks_u8(self, sig):
+        """sig: CUDA uint8 [n, 64] -> CUDA uint8 [n, 64], every signature's cells ranked 0..63, ties by index (engine.signature_ranks)."""
+        return self.engine.signature_ranks(sig)
+
+    def align_moments_u8(self, library, frames, canvas_hw, first, span, geom):
+        """align_residuals_u8's arguments -> int64 [m, span, 6] on device: (count, sum l, sum s, sum l^2, sum s^2, sum l s) of frame
+        i's warped luma l against the luma s of library[first[i] + j] under ``geom`` (engine.align_moments)."""
+        if tuple(int(v) for v in library.shape[1:3]) != (int(canvas_hw[0]), int(canvas_hw[1])):
+            raise ValueError("the library frames must have the canvas's size")
+        return self.engine.align_moments(library, frames, first, span, geom)
+
     # -- leaks whose brightness, contrast or gamma changed (build extension: offmark.tone.read_toned_leak) -----------------------------
     def histograms_u8(self, frames):
         """frames: CUDA uint8 [n, h, w, 3] -> int64 [n, 3, 256] on device, the per-channel histograms (engine.histograms)."""

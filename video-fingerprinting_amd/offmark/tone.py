@@ -14,8 +14,11 @@ The histogram match alone does not restore the mark (it brings the geometry to a
 conditional curve does.  Host side, NumPy and Python integers, deterministic: the device and the statement (tests/_tone.py) hand the
 same integers in, so the same tables and geometries come out.
 
+read_toned_leak needs sources[i] to be leak frame i's source; for a CLIP whose tone changed, offmark.temporal.read_toned_leak_clip finds
+that map first (its signatures and its frame cost are tone invariant; read_leak_clip's are not) and then calls read_toned_leak.
+
 Not handled: a curve that varies over the clip or over the frame (vignetting), cross-talk between channels (hue, saturation), the DCT
-codec, 4:2:0 planes, blk 8, and offmark.temporal.read_leak_clip under a tone change (its signatures are not tone invariant)."""
+codec, 4:2:0 planes, blk 8."""
 import numpy as np
 
 from . import resync
@@ -70,6 +73,20 @@ def _isotonic(sums, counts) -> list:
     return out
 
 
+def curve_of_sums(sums) -> np.ndarray:
+    """One channel of lut_of_sums: int64 [256, 2] = (count, sum of target values) per value -> uint8 [256], non-decreasing.  Also the
+    curve between two signature lists (offmark.temporal.signature_lut)."""
+    t = _table(sums, (LEVELS, 2), "sums")
+    if (t < 0).any():
+        raise ValueError("sums must not be negative")
+    have = np.flatnonzero(t[:, 0] > 0)
+    if have.size < 2:
+        return np.arange(LEVELS, dtype=np.uint8)
+    fit = _isotonic(t[have, 1], t[have, 0])
+    levels = np.arange(LEVELS, dtype=np.float64)
+    return np.clip(np.rint(np.interp(levels, have.astype(np.float64), np.asarray(fit, np.float64))), 0, 255).astype(np.uint8)
+
+
 def lut_of_sums(sums) -> np.ndarray:
     """The tone curve of decoder.tone_sums_u8's sums at one candidate: int64 [3, 256, 2] = (count, sum of source values) per channel
     and leak value, summed over frames.  Per channel: the levels with a count carry the mean sum / count; a weighted non-decreasing
@@ -79,16 +96,7 @@ def lut_of_sums(sums) -> np.ndarray:
     t = _table(sums, (3, LEVELS, 2), "sums")
     if (t < 0).any():
         raise ValueError("sums must not be negative")
-    lut = np.empty((3, LEVELS), np.uint8)
-    levels = np.arange(LEVELS, dtype=np.float64)
-    for c in range(3):
-        have = np.flatnonzero(t[c, :, 0] > 0)
-        if have.size < 2:
-            lut[c] = np.arange(LEVELS)
-            continue
-        fit = _isotonic(t[c, have, 1], t[c, have, 0])
-        lut[c] = np.clip(np.rint(np.interp(levels, have.astype(np.float64), np.asarray(fit, np.float64))), 0, 255).astype(np.uint8)
-    return lut
+    return np.stack([curve_of_sums(t[c]) for c in range(3)])
 
 
 def _frame_sum(a) -> np.ndarray:
