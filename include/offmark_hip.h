@@ -772,6 +772,43 @@ int ofmk_tone_sums_rgb8(const uint8_t *src, const uint8_t *leak, int n, int h, i
                         long long *sums, void *stream, const ofmk_opts *opts);
 int ofmk_apply_tone_rgb8(const uint8_t *in, int n, int h, int w, const uint8_t *lut, uint8_t *out, void *stream, const ofmk_opts *opts);
 
+/* ---- reading a leak whose COLOURS changed: a matrix fitted against the SOURCE frames (BUILD EXTENSION) --------------------------
+ * A BT.601 / BT.709 mix-up, a saturation setting or a hue shift is a 3 x 3 matrix plus an offset on RGB.  No per-channel curve undoes
+ * a matrix, and the DwtDctSvd mark lives in U, a difference of channels: it leaves its cell 15 wide as soon as the channels mix.  The
+ * operator holds the source frames, so the matrix that takes the leak's pixels back to the source's is fitted to them by least squares
+ * (offmark.colour.read_coloured_leak), as the tone curve is: a histogram match for a first registration, then the sums below under
+ * the registered geometry, an exact solve on the host, and the matrix applied in integers.  Interleaved u8 RGB; the codec takes no
+ * part.  Everything is an integer, so the device equals the NumPy statement (tests/_colour.py) exactly.
+ *
+ * ofmk_colour_sums_rgb8: the arguments of ofmk_tone_sums_rgb8 -- src is device u8 [n][H][W][3], src[f] the source of leak frame f;
+ *   leak is device u8 [n][h][w][3]; cands is DEVICE memory, ofmk_affine [K] -- and sums is device int64 [n][K][28], cleared by the call
+ *   whatever it held.  Canvas pixel (y, x) contributes iff it is inside the leak by ofmk_affine's per-pixel rule (no border is left
+ *   out) AND the three bytes l that ofmk_warp_affine_rgb8 would write there under cands[k] all lie in 1..254: a clipped pixel says
+ *   nothing about the matrix and bends the fit.  With s = src[f][y][x]:
+ *       sums[f][k][0] += 1      sums[f][k][1 + c] += l[c]      sums[f][k][4 + c] += s[c]
+ *       sums[f][k][7..12] += l[i] * l[j]      sums[f][k][13..18] += s[i] * s[j]      for (i, j) = (0,0) (0,1) (0,2) (1,1) (1,2) (2,2)
+ *       sums[f][k][19 + 3 * i + j] += l[i] * s[j]
+ *   the normal equations of s ~ M l + t and what its residual needs.  A candidate out of ofmk_affine's range leaves 28 zeros (the list
+ *   is not read on the host).  A workgroup owns a tile of 64 x 64 canvas pixels of one candidate and one frame and leaves at once when
+ *   the tile lies wholly beyond one edge of the leak; the taps are formed as in ofmk_align_sums_rgb8 and no warped frame is written.
+ *   28 sums per thread in registers, then the wavefront and LDS in 32 unsigned bits (a tile's sums stay below 4096 * 255^2 < 2^28),
+ *   then at most 28 64-bit atomics per workgroup -- integer adds, so the result does not depend on their order.  Candidates in
+ *   gridDim.y and frames in gridDim.z, chunked at 65535 and below 2^30 workgroups per launch.  Required, else OFMK_E_ARG: n >= 1,
+ *   8 <= H, W <= 4096, h, w >= 1 with h*w < 2^28, K >= 1, n*K < 2^40, no null pointer.
+ * ofmk_apply_colour_rgb8: in is device u8 [n][h][w][3]; matrix is HOST int32 [3][4] in Q16, row c the three coefficients and then the
+ *   offset, read by the call and handed to the kernel by value; out is device u8 [n][h][w][3], every byte written:
+ *       out[f][y][x][c] = clip((m[c][0] * in[0] + m[c][1] * in[1] + m[c][2] * in[2] + m[c][3] + 32768) >> 16, 0, 255)
+ *   with in[.] the three bytes of in[f][y][x] and an arithmetic shift.  |coefficient| <= 2^21 and |offset| <= 2^28, else OFMK_E_ARG:
+ *   the sum then stays inside int32.  out == in (exactly) is allowed; any other overlap is not.  12 bytes = four pixels per thread as
+ *   three dwords at any address, in and out; no alignment is assumed.  Required, else OFMK_E_ARG: n >= 1, h, w >= 1 with h*w < 2^28,
+ *   no null pointer, a matrix in range.
+ * Both calls allocate nothing, synchronise nothing and are graph capturable (a captured ofmk_apply_colour_rgb8 keeps the matrix it was
+ * captured with); both are timed as kind 4 (svd); the flags are ignored. */
+int ofmk_colour_sums_rgb8(const uint8_t *src, const uint8_t *leak, int n, int h, int w, int H, int W, const ofmk_affine *cands, int K,
+                          long long *sums, void *stream, const ofmk_opts *opts);
+int ofmk_apply_colour_rgb8(const uint8_t *in, int n, int h, int w, const int32_t *matrix /* HOST, [3][4] */, uint8_t *out, void *stream,
+                           const ofmk_opts *opts);
+
 /* ---- DeShuffler.degenerate's epilogue for a batch, on the device ---------------------------
  * src/offmark/degenerator/de_shuffler.py:17-22: mean of bits[i::L] (from `counts`), undo the key
  * permutation (`perm` = DeShuffler.payload_idx, device int32 [L]), threshold strictly above the

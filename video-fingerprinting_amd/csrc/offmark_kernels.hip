@@ -56,6 +56,7 @@
 #include "align_kernels.hiph"
 #include "temporal_kernels.hiph"
 #include "tone_kernels.hiph"
+#include "colour_kernels.hiph"
 
 namespace {
 
@@ -2162,6 +2163,57 @@ int ofmk_apply_tone_rgb8(const uint8_t *in, int n, int h, int w, const uint8_t *
     const unsigned grid = (unsigned)(steps < 1 ? 1 : steps > 32768 ? 32768 : steps);      // beyond that a thread walks several groups
     ScopedTiming timing(KIND_SVD, cx);
     OFMK_TIMED_LAUNCH(timing, apply_tone_rgb8_kernel, dim3(grid), dim3(kThreads), 0, cx.s, in, out, lut, bytes);
+    HIP_TRY(hipGetLastError());
+    return OFMK_OK;
+}
+
+// ---- leaks whose colours changed: a matrix fitted against the source frames (colour_kernels.hiph; build extensions) ------------------
+// sums[f][k][0..27] = the least-squares sums of source frame f against leak frame f warped by cands[k] (DEVICE memory, [K]) over the
+// canvas pixels inside the leak whose warped bytes are all in 1..254; int64 [n][K][28], cleared here whatever it held; an out-of-range
+// candidate leaves 28 zeros.  Chunks as ofmk_align_sums_rgb8.
+int ofmk_colour_sums_rgb8(const uint8_t *src, const uint8_t *leak, int n, int h, int w, int H, int W, const ofmk_affine *cands, int K,
+                          long long *sums, void *stream, const ofmk_opts *opts) {
+    if (int rc = check_search_args(opts, n, h, w, H, W, src && leak && cands && sums, K, kAlignMaxSide)) return rc;
+    const Ctx cx = make_ctx(stream, opts);
+    HIP_TRY(launch_zero(sums, (size_t)n * K * kColourSums * sizeof(long long), cx.s));
+    AlignArgs a;
+    a.h = h; a.w = w; a.H = H; a.W = W;
+    a.tiles_x = (W + kAlignTile - 1) / kAlignTile;
+    a.K = K;
+    a.leak_stride = (size_t)h * w * 3;
+    a.src_stride = (size_t)H * W * 3;
+    const long long tiles = (long long)a.tiles_x * ((H + kAlignTile - 1) / kAlignTile);
+    const AffineMap *dc = reinterpret_cast<const AffineMap *>(cands);
+    for_cand_frame_chunks(tiles, K, n, [&](int k0, int ck, int f0, int cf) {
+        ScopedTiming timing(KIND_SVD, cx);
+        OFMK_TIMED_LAUNCH(timing, colour_sums_rgb8_kernel, dim3((unsigned)tiles, (unsigned)ck, (unsigned)cf), dim3(kThreads), 0, cx.s,
+                          src + (size_t)f0 * a.src_stride, leak + (size_t)f0 * a.leak_stride, dc + k0, a,
+                          reinterpret_cast<unsigned long long *>(sums) + ((size_t)f0 * K + k0) * kColourSums);
+        return OFMK_OK;
+    });
+    HIP_TRY(hipGetLastError());
+    return OFMK_OK;
+}
+
+// out[c] = clip((m[c][0] in[0] + m[c][1] in[1] + m[c][2] in[2] + m[c][3] + 32768) >> 16, 0, 255) per pixel: u8 [n][h][w][3], every byte
+// written; matrix is HOST int32 [3][4] in Q16, read here and passed by value; out == in is allowed.
+int ofmk_apply_colour_rgb8(const uint8_t *in, int n, int h, int w, const int32_t *matrix, uint8_t *out, void *stream, const ofmk_opts *opts) {
+    if (int orc = check_opts(opts)) return orc;
+    if (n <= 0) return fail(OFMK_E_ARG, "n must be positive%s");
+    if (int rc = check_leak_dims(h, w)) return rc;
+    if (!in || !matrix || !out) return fail(OFMK_E_ARG, "null pointer%s");
+    ColourMatrix cm;
+    for (int c = 0; c < 3; ++c)
+        for (int j = 0; j < 4; ++j) {
+            const long long v = matrix[4 * c + j], lim = j < 3 ? (1LL << 21) : (1LL << 28);     // the sum stays inside int32
+            if (v < -lim || v > lim) return fail(OFMK_E_ARG, "matrix: |coefficient| <= 2^21 and |offset| <= 2^28%s");
+            cm.m[c][j] = (int32_t)v;
+        }
+    const Ctx cx = make_ctx(stream, opts);
+    const size_t bytes = (size_t)n * h * w * 3, steps = (bytes / 12 + kThreads - 1) / kThreads;
+    const unsigned grid = (unsigned)(steps < 1 ? 1 : steps > 32768 ? 32768 : steps);      // beyond that a thread walks several groups
+    ScopedTiming timing(KIND_SVD, cx);
+    OFMK_TIMED_LAUNCH(timing, apply_colour_rgb8_kernel, dim3(grid), dim3(kThreads), 0, cx.s, in, out, cm, bytes);
     HIP_TRY(hipGetLastError());
     return OFMK_OK;
 }

@@ -137,6 +137,8 @@ SIGNATURES = {
     "ofmk_histograms_rgb8":(_i32, [_vp, _i32, _i32, _i32, _vp, _vp, _op]),
     "ofmk_tone_sums_rgb8": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _op]),
     "ofmk_apply_tone_rgb8": (_i32, [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _op]),
+    "ofmk_colour_sums_rgb8": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _op]),
+    "ofmk_apply_colour_rgb8": (_i32, [_vp, _i32, _i32, _i32, C.POINTER(C.c_int32), _vp, _vp, _op]),      # the matrix: HOST int32 [3][4]
     "ofmk_probe_xcc":(_i32, [_vp, _i32, _vp, _op]),
     "ofmk_hbm_copy": (_i32, [_vp, _vp, _sz, _vp]),
     "ofmk_hbm_read": (_i32, [_vp, _sz, _vp, _vp]),

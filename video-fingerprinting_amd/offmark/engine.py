@@ -888,6 +888,41 @@ class DctEngine:
         _hip.check(self.lib.ofmk_apply_tone_rgb8(frames.data_ptr(), n, h, w, lut.data_ptr(), out.data_ptr(), _hip.current_stream(), self._o()))
         return out
 
+    # -- leaks whose colours changed: a matrix fitted against the source frames (build extension; offmark.colour) ----------------------
+    def colour_sums(self, sources, frames, cands, sums=None):
+        """The 28 least-squares sums of source ~ M leak + t per frame and candidate (ofmk_colour_sums_rgb8).  sources: uint8
+        [n, H, W, 3], H, W <= 4096; frames: uint8 [n, h, w, 3]; ``cands``: int64 [K, 6], a tensor on this device or an array (copied
+        there) -> int64 [n, K, 28] over the canvas pixels inside the leak whose three warped bytes l all lie in 1..254, s the source's
+        bytes there: [0] the count, [1..3] sum l, [4..6] sum s, [7..12] sum l_i l_j and [13..18] sum s_i s_j for (i, j) = 00 01 02 11
+        12 22, [19 + 3 i + j] sum l_i s_j; a candidate out of range has zeros.  No warped frame is written."""
+        t = self.torch
+        n, H, W = self._check_frames(sources, t.uint8)
+        m, h, w = self._check_frames(frames, t.uint8)
+        if m != n:
+            raise ValueError("one source frame per leak frame")
+        cands, K = self._cands(cands, 6)
+        sums = self._buffer("sums", sums, (n, K, 28), t.int64, self.device)
+        _hip.check(self.lib.ofmk_colour_sums_rgb8(sources.data_ptr(), frames.data_ptr(), n, h, w, H, W, cands.data_ptr(), K, sums.data_ptr(),
+                                                  _hip.current_stream(), self._o()))
+        return sums
+
+    def apply_colour(self, frames, matrix, out=None):
+        """out[.., c] = clip((m[c, 0] r + m[c, 1] g + m[c, 2] b + m[c, 3] + 32768) >> 16, 0, 255) per pixel: uint8 [n, h, w, 3] -> uint8
+        [n, h, w, 3]; ``matrix``: integers [3, 4] in Q16 on the HOST, |coefficient| <= 2^21 and |offset| <= 2^28 (else ValueError);
+        ``out`` may be ``frames`` itself (ofmk_apply_colour_rgb8)."""
+        t = self.torch
+        n, h, w = self._check_frames(frames, t.uint8)
+        m = np.asarray(matrix.cpu() if isinstance(matrix, t.Tensor) else matrix)
+        if m.shape != (3, 4) or m.dtype.kind not in "iu":
+            raise ValueError("matrix must be integers of shape [3, 4]")
+        if (np.abs(m[:, :3].astype(np.int64)) > 1 << 21).any() or (np.abs(m[:, 3].astype(np.int64)) > 1 << 28).any():
+            raise ValueError("matrix: |coefficient| <= 2^21 and |offset| <= 2^28")
+        m = np.ascontiguousarray(m, dtype=np.int32)
+        out = self._out(out, frames)
+        _hip.check(self.lib.ofmk_apply_colour_rgb8(frames.data_ptr(), n, h, w, m.ctypes.data_as(C.POINTER(C.c_int32)), out.data_ptr(),
+                                                   _hip.current_stream(), self._o()))
+        return out
+
     def svd_embed_detect(self, frames, wm, L, scale=15, wm_row=None, out=None, want_bits=False, scales=None, blk=4, counts=None,
                          partial=False):
         t = self.torch

@@ -144,6 +144,19 @@ class DwtDctSvdDecoder:
         (engine.apply_tone)."""
         return self.engine.apply_tone(frames, lut)
 
+    # -- leaks whose colours changed: a BT.601 / 709 mix-up, saturation, hue (build extension: offmark.colour.read_coloured_leak) ------
+    def colour_sums_u8(self, sources, frames, canvas_hw, cands):
+        """sources: CUDA uint8 [n, H, W, 3] with (H, W) = canvas_hw, frames: CUDA uint8 [n, h, w, 3], cands: int64 [K, 6] -> int64
+        [n, K, 28] on device: the least-squares sums of source ~ M leak + t over the unclipped pixels (engine.colour_sums)."""
+        if tuple(int(v) for v in sources.shape[1:3]) != (int(canvas_hw[0]), int(canvas_hw[1])):
+            raise ValueError("the source frames must have the canvas's size")
+        return self.engine.colour_sums(sources, frames, cands)
+
+    def apply_colour_u8(self, frames, matrix):
+        """frames: CUDA uint8 [n, h, w, 3], matrix: host int32 [3, 4] in Q16 -> CUDA uint8 [n, h, w, 3], the matrix and offset applied to
+        every pixel in integers (engine.apply_colour)."""
+        return self.engine.apply_colour(frames, matrix)
+
     def sync_scores_planes_yuv420(self, planes, height, width, layout="i420"):
         """planes: CUDA uint8 [n, 1.5*H*W] (I420 or NV12), even H, W >= 8 -> int64 [n, 64] on device: sync_scores_u8's sums at the
         phases with even py and px, 0 elsewhere -- an odd crop offset does not exist on 4:2:0 planes (engine.svd_sync_scores_yuv420)."""

@@ -29,7 +29,8 @@ dissolve brightness IS time, so the plain thumbnail's strongest cue moves, and s
            nearly-right sources absorbs the brightness error of a frame that is one off.
 
 What neither can do: clips re-cut out of order or reversed (the path is monotone); a tone curve that varies over the clip or over the
-frame, or cross-talk between channels; static content, where time is not observable, and pure pans, where a time shift and a crop offset
+frame, or cross-talk between channels (for a leak whose frames are already matched, offmark.colour.read_coloured_leak fits the colour
+matrix; for a clip it is not built); static content, where time is not observable, and pure pans, where a time shift and a crop offset
 are the same thing; the DCT codec, 4:2:0 planes, blk 8."""
 from __future__ import annotations
 

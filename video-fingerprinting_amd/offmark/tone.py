@@ -17,8 +17,9 @@ same integers in, so the same tables and geometries come out.
 read_toned_leak needs sources[i] to be leak frame i's source; for a CLIP whose tone changed, offmark.temporal.read_toned_leak_clip finds
 that map first (its signatures and its frame cost are tone invariant; read_leak_clip's are not) and then calls read_toned_leak.
 
-Not handled: a curve that varies over the clip or over the frame (vignetting), cross-talk between channels (hue, saturation), the DCT
-codec, 4:2:0 planes, blk 8."""
+Cross-talk between channels (hue, saturation, a BT.601 / BT.709 mix-up) is no curve: offmark.colour.read_coloured_leak fits a matrix to
+the sources instead.  Not handled: a curve that varies over the clip or over the frame (vignetting), a matrix followed by a gamma, the
+DCT codec, 4:2:0 planes, blk 8."""
 import numpy as np
 
 from . import resync
