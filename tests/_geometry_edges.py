@@ -258,6 +258,31 @@ def out_of_range4():
     return [(MIN_A - 1, 0, ONE, 0), (ONE, 0, MAX_A + 1, 0), (ONE, MAX_B + 1, ONE, 0)]
 
 
+def interleaved(maps, bad):
+    """The maps with the out-of-range ones put between them: (list, indices of the good ones, indices of the bad ones)."""
+    out = list(maps)
+    for k, b in enumerate(bad):
+        out.insert(min(len(out), 1 + k * max(1, len(maps) // len(bad))), b)
+    bad_at = [k for k, g in enumerate(out) if any(g is b for b in bad)]
+    return out, [k for k in range(len(out)) if k not in bad_at], bad_at
+
+
+# ---- the cases of the registration calls and of everything else that walks align_kernels.hiph's 64 x 64 tile ---------------------
+# (leak, canvas, maps), at most 16 maps each: test_gpu_geometry_edges.py (align_sums, align_residuals), test_gpu_value_edges.py
+ALIGN_CASES = {
+    "steepest": (STEEP_LEAK, CANVAS, steepest(64)[:16]), "uniform": (STEEP_LEAK, CANVAS, uniform(64)[:15]),
+    "smallest-determinant": (ODD_LEAK, CANVAS, smallest_determinant(32)[::2]), "anisotropic": (STEEP_LEAK, CANVAS, anisotropic(16)[:12]),
+    "boundary": (ODD_LEAK, SMALL_CANVAS, boundary(ODD_LEAK)[::5]),
+    "boundary-1x83": ((1, 83), SMALL_CANVAS, boundary((1, 83))[1::5]), "boundary-61x2": ((61, 2), SMALL_CANVAS, boundary((61, 2))[2::5]),
+    "boundary-3x3": ((3, 3), SMALL_CANVAS, boundary((3, 3))[3::5]), "tiny-3x2": ((3, 2), SMALL_CANVAS, tiny((3, 2))[:12]),
+    "tiny-1x83": ((1, 83), SMALL_CANVAS, tiny((1, 83))[4:]),
+    "far-wide": (WIDE_LEAK, ALIGN_LONG_CANVAS, far(WIDE_LEAK, ALIGN_LONG_CANVAS, ALIGN_FAR_X)),
+    "far-tall": (TALL_LEAK, ALIGN_LONG_CANVAS, far(TALL_LEAK, ALIGN_LONG_CANVAS, ALIGN_FAR_X)),
+}
+RESIDUAL_MAPS = [("steepest", 0), ("steepest", 5), ("uniform", 3), ("smallest-determinant", 1), ("anisotropic", 2), ("boundary", 7), ("boundary-61x2", 9),
+                 ("far-wide", 4), ("far-tall", 3)]
+
+
 # ---- the mirror identity ------------------------------------------------------------------------------------------------------------
 def mirrored(g, w):
     """The map that reads, in the leak mirrored left to right, the sample ``g`` reads in the leak: pos_x' = ((w - 1) << 16) - pos_x.

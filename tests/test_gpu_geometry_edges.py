@@ -65,13 +65,7 @@ def six(g4):
     return ay, 0, by, 0, ax, bx
 
 
-def interleaved(maps, bad):
-    """The maps with the out-of-range ones put between them: (list, indices of the good ones, indices of the bad ones)."""
-    out = list(maps)
-    for k, b in enumerate(bad):
-        out.insert(min(len(out), 1 + k * max(1, len(maps) // len(bad))), b)
-    bad_at = [k for k, g in enumerate(out) if any(g is b for b in bad)]
-    return out, [k for k in range(len(out)) if k not in bad_at], bad_at
+interleaved = ge.interleaved
 
 
 # (leak, canvas, maps) of every affine family, at most 64 maps each
@@ -247,16 +241,7 @@ def test_phase_scores_and_units_equal_the_64_shifted_maps(eng, leaks, case):
 
 
 # ---- 4. the registration sums and the residuals ---------------------------------------------------------------------------------------
-ALIGN_CASES = {
-    "steepest": (ge.STEEP_LEAK, ge.CANVAS, ge.steepest(64)[:16]), "uniform": (ge.STEEP_LEAK, ge.CANVAS, ge.uniform(64)[:15]),
-    "smallest-determinant": (ge.ODD_LEAK, ge.CANVAS, ge.smallest_determinant(32)[::2]), "anisotropic": (ge.STEEP_LEAK, ge.CANVAS, ge.anisotropic(16)[:12]),
-    "boundary": (ge.ODD_LEAK, ge.SMALL_CANVAS, ge.boundary(ge.ODD_LEAK)[::5]),
-    "boundary-1x83": ((1, 83), ge.SMALL_CANVAS, ge.boundary((1, 83))[1::5]), "boundary-61x2": ((61, 2), ge.SMALL_CANVAS, ge.boundary((61, 2))[2::5]),
-    "boundary-3x3": ((3, 3), ge.SMALL_CANVAS, ge.boundary((3, 3))[3::5]), "tiny-3x2": ((3, 2), ge.SMALL_CANVAS, ge.tiny((3, 2))[:12]),
-    "tiny-1x83": ((1, 83), ge.SMALL_CANVAS, ge.tiny((1, 83))[4:]),
-    "far-wide": (ge.WIDE_LEAK, ge.ALIGN_LONG_CANVAS, ge.far(ge.WIDE_LEAK, ge.ALIGN_LONG_CANVAS, ge.ALIGN_FAR_X)),
-    "far-tall": (ge.TALL_LEAK, ge.ALIGN_LONG_CANVAS, ge.far(ge.TALL_LEAK, ge.ALIGN_LONG_CANVAS, ge.ALIGN_FAR_X)),
-}
+ALIGN_CASES = ge.ALIGN_CASES                # shared with test_gpu_value_edges.py
 
 
 @pytest.mark.parametrize("case", ALIGN_CASES)
@@ -273,8 +258,7 @@ def test_align_sums_equal_the_statement(eng, leaks, case):
     assert not want[:, bad].any() and want[:, good, 28].all() and (want[:, good, 27] > 0).all()
 
 
-RESIDUAL_MAPS = [("steepest", 0), ("steepest", 5), ("uniform", 3), ("smallest-determinant", 1), ("anisotropic", 2), ("boundary", 7), ("boundary-61x2", 9),
-                 ("far-wide", 4), ("far-tall", 3)]
+RESIDUAL_MAPS = ge.RESIDUAL_MAPS
 
 
 @pytest.mark.parametrize("span", [1, 16])
